@@ -27,6 +27,11 @@ line of the same shape with metric particle-steps/s.
 `value` is the step-loop rate (K launches between barrier + synchronize on both sides).  The
 reference's timed region also holds the final sync_host (8 D2H copies, xrays_bench.cpp:95-102);
 that PCIe-inclusive rate of the same run is `value_with_sync_host`.
+
+The warm-up runs for a time (--warmup-seconds), so the state is put back to what the init left before the
+timed steps: the same arguments give the timed steps the same inputs on every run.  `--dump-outputs DIR`
+writes what the last timed step left (a fixed, seeded sample of the ensemble) as DIR/<name>.npy, so that
+two builds can be compared output for output.
 """
 import argparse
 import json
@@ -51,6 +56,8 @@ HBM_PEAK_GBPS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 DEFAULT_RAYS_ONE_GPU = 10000000   # north_star: "1e7 cold-plasma rays at 1 MI355X"
 DEFAULT_TOTAL_RAYS = 100000000    # BASELINE configs[3]
 BENCH_RAY = dict(t=0.0, w=500.0, x=2.5, y=0.0, z=0.0, kx=-600.0, ky=0.0, kz=0.0)
+DUMP_SAMPLE = 1 << 19             # --dump-outputs: rays (particles) sampled; 9 fp64 arrays + the indices = 40 MiB
+DUMP_SEED = 0
 
 
 def parse_arguments(argv=None):
@@ -89,7 +96,14 @@ def parse_arguments(argv=None):
     parser.add_argument("--distribution", choices=["bench", "cli"], default="bench",
                         help="bench: identical rays of xrays_bench.cpp:62-71 (the metric's workload); "
                              "cli: the incoherent example distribution of graph_driver/xrays.cpp (BASELINE configs[2])")
-    return parser.parse_args(argv)
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write the arrays the last timed step left (the state a caller gets "
+                             "from sync_host, and the residual) as DIR/<name>.npy; a fixed, seeded sample of at most "
+                             "%d rays (particles) of the ensemble, with its indices in DIR/sample_index.npy" % DUMP_SAMPLE)
+    args = parser.parse_args(argv)
+    if args.steps < 1:
+        parser.error("--steps must be at least 1")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------
@@ -242,6 +256,50 @@ def sample_statistics(samples):
     quarter = max(1, len(samples)//4)
     return {"min": ordered[0], "median": ordered[len(ordered)//2], "max": ordered[-1],
             "first_quarter_mean": sum(samples[:quarter])/quarter, "last_quarter_mean": sum(samples[-quarter:])/quarter}
+
+
+def snapshot(tensors):
+    """Device copies of the state tensors: the timed steps start from this state whatever the warm-up did."""
+    import torch
+    torch.cuda.synchronize()
+    saved = {k: t.clone() for k, t in tensors.items()}
+    torch.cuda.synchronize()
+    return saved
+
+
+def restore(tensors, saved):
+    import torch
+    torch.cuda.synchronize()
+    for k, t in tensors.items():
+        t.copy_(saved[k])
+    torch.cuda.synchronize()
+
+
+def dump_outputs(directory, tensors, total, rank, world):
+    """--dump-outputs: DIR/<name>.npy for every tensor of the state the last timed step left, on the whole ensemble
+    (all-gathered over the ranks), sampled at DUMP_SAMPLE fixed seeded indices when it is larger; the indices go to
+    DIR/sample_index.npy (float64, exact below 2**53).  Collective: every rank calls it, rank 0 writes."""
+    import numpy as np
+    import torch
+    from graph_framework_amd import distributed as gfd
+    if total > DUMP_SAMPLE:
+        index = np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_SAMPLE, replace=False))
+    else:
+        index = np.arange(total)
+    gathered = {}
+    for name, local in tensors.items():
+        if world > 1:
+            shard = local if torch.distributed.get_backend() == "nccl" else local.cpu()
+            local = gfd.all_gather_shards(shard, total)
+        if rank == 0:
+            gathered[name] = local[torch.from_numpy(index).to(local.device)].cpu().numpy()
+        del local
+    if rank != 0:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, values in gathered.items():
+        np.save(os.path.join(directory, name + ".npy"), values)
+    np.save(os.path.join(directory, "sample_index.npy"), index.astype(np.float64))
 
 
 def cpu_baseline(target_seconds=12.0):
@@ -503,6 +561,7 @@ def run_rank_korc(args):
                    index=local_rank, items=items, device_state=True)
     push.compile()
     push.pre_run()
+    initial = snapshot(push.device)
     warm_start = time.perf_counter()
     warm_steps = 0
     for _ in range(args.warmup):
@@ -514,6 +573,9 @@ def run_rank_korc(args):
             push.run()
         warm_steps += 10
         torch.cuda.synchronize()
+#  The warm-up runs for a time, not a count: the timed steps start again from the state pre_run left.
+    restore(push.device, initial)
+    del initial
     timing_period = 8 if args.steps >= 64 else 1
     push.work.context.enable_timing(True, every=timing_period)
 
@@ -528,6 +590,8 @@ def run_rank_korc(args):
     samples = push.step_item.kernel.timing_samples()
     kernel_ms = gfd.max_over_ranks(sum(samples)/len(samples) if samples else 0.0)
     push.work.context.enable_timing(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, push.device, total, rank, world)
 
     gather_seconds = None
     checksum = None
@@ -659,6 +723,7 @@ def run_rank(args):
                 % (solve.newton_iterations + 1, newton_batch, newton_wall)})
     solve.work.context.enable_timing(False)
 
+    initial = snapshot(solve.device)
     warm_start = time.perf_counter()
     warm_steps = 0
     for _ in range(args.warmup):
@@ -670,6 +735,10 @@ def run_rank(args):
             solve.step()
         warm_steps += 10
         torch.cuda.synchronize()
+#  The warm-up runs for a time, not a count: the timed steps start again from the state the Newton init left, so
+#  that the same arguments give the timed steps the same inputs on every run.
+    restore(solve.device, initial)
+    del initial
 #  HIP events on the launch stream around every 8th step of the timed region (an event pair
 #  costs the stream 2-8 us; around every launch they would slow the loop they measure by 1-3 %).
     timing_period = 8 if args.steps >= 64 else 1
@@ -694,6 +763,8 @@ def run_rank(args):
     launches = len(samples)
     kernel_ms = gfd.max_over_ranks(kernel_ms)
     solve.work.context.enable_timing(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solve.device, total, rank, world)
 
 #  Output-cadence collective: all-gather of the trajectory state over xGMI, from the device
 #  tensors the kernels write (not in the step loop; gloo rehearsals gather host copies).

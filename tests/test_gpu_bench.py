@@ -95,3 +95,79 @@ def test_korc_leg_two_ranks_on_one_gpu():
     assert two["all_gather_bytes"] == 1000001*4*7
     assert two["all_gather_checksum"] == one["all_gather_checksum"]
     assert two["config"]["b0"] == one["config"]["b0"]
+
+
+def _dumped(directory):
+    import numpy as np
+    return {name[:-4]: np.load(os.path.join(directory, name)) for name in sorted(os.listdir(directory))}
+
+
+def test_dump_outputs_are_the_state_of_the_last_timed_step(tmp_path):
+    """--dump-outputs writes what the timed steps computed: the same arrays as a direct run of --steps RK4 steps from
+    the Newton init, bit for bit, whatever the warm-up did before the timed region."""
+    import numpy as np
+    import torch
+    from graph_framework_amd.xrays import Rk4ColdPlasmaEfit, STATE
+    rays, steps = 200000, 7
+    arguments = ["--rays-per-gpu", str(rays), "--steps", str(steps), "--no-cpu-baseline", "--no-extra"]
+    line = _bench(arguments + ["--warmup", "2", "--warmup-seconds", "0.05", "--dump-outputs", str(tmp_path/"a")])
+    _bench(arguments + ["--warmup", "5", "--warmup-seconds", "0.3", "--dump-outputs", str(tmp_path/"b")])
+    assert line["steps"] == steps and line["ms_per_step"] > 0.0
+    a, b = _dumped(tmp_path/"a"), _dumped(tmp_path/"b")
+    assert sorted(a) == sorted(STATE + ("residual", "sample_index"))
+    for name in a:
+        assert a[name].dtype == np.float64 and a[name].shape == (rays,), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    np.testing.assert_array_equal(a["sample_index"], np.arange(rays))
+
+    solve = Rk4ColdPlasmaEfit({k: np.full(rays, v) for k, v in
+                               dict(t=0.0, w=500.0, x=2.5, y=0.0, z=0.0, kx=-600.0, ky=0.0, kz=0.0).items()},
+                              device_state=True)
+    solve.init("kx")
+    solve.compile()
+    for _ in range(steps):
+        solve.step()
+    host = solve.sync_host()
+    torch.cuda.synchronize()
+    residual = solve.device["residual"].cpu().numpy()
+    solve.work.context.close()
+    for k in STATE:
+        np.testing.assert_array_equal(a[k], host[k], err_msg=k)
+    np.testing.assert_array_equal(a["residual"], residual)
+    assert a["t"][0] != 0.0
+
+
+def test_dump_outputs_sample_a_large_ensemble_at_fixed_indices(tmp_path):
+    """Above bench.DUMP_SAMPLE rays the dump is a seeded sample: the same indices on every run, the values of those rays."""
+    import numpy as np
+    import bench
+    from graph_framework_amd.xrays import Rk4ColdPlasmaEfit, STATE, cli_distribution
+    rays, steps = bench.DUMP_SAMPLE + 100003, 3
+    _bench(["--distribution", "cli", "--rays-per-gpu", str(rays), "--steps", str(steps), "--warmup", "2",
+            "--warmup-seconds", "0.05", "--no-cpu-baseline", "--no-extra", "--dump-outputs", str(tmp_path)])
+    dump = _dumped(tmp_path)
+    index = dump["sample_index"].astype(np.int64)
+    assert index.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(index) > 0) and 0 <= index[0] and index[-1] < rays
+    assert sum(os.path.getsize(tmp_path/name) for name in os.listdir(tmp_path)) <= 64*2**20
+    solve = Rk4ColdPlasmaEfit(cli_distribution(rays, seed=0), device_state=True)
+    solve.init("kx")
+    solve.compile()
+    for _ in range(steps):
+        solve.step()
+    host = solve.sync_host()
+    solve.work.context.close()
+    for k in STATE:
+        np.testing.assert_array_equal(dump[k], host[k][index], err_msg=k)
+
+
+def test_korc_dump_outputs_do_not_depend_on_the_warm_up(tmp_path):
+    import numpy as np
+    from graph_framework_amd import korc as gk
+    arguments = ["--workload", "korc", "--total-rays", "100000", "--steps", "5", "--no-cpu-baseline"]
+    _bench(arguments + ["--warmup", "1", "--warmup-seconds", "0.0", "--dump-outputs", str(tmp_path/"a")])
+    _bench(arguments + ["--warmup", "4", "--warmup-seconds", "0.2", "--dump-outputs", str(tmp_path/"b")])
+    a, b = _dumped(tmp_path/"a"), _dumped(tmp_path/"b")
+    assert sorted(a) == sorted(tuple(gk.PARTICLE) + ("sample_index",))
+    for k in gk.PARTICLE:
+        assert a[k].dtype == np.float32 and a[k].shape == (100000,)
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
