@@ -24,7 +24,9 @@
 #include <limits>
 #include <map>
 #include <memory>
+#include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gf_hip.h"
@@ -45,12 +47,43 @@ namespace {
 
 thread_local std::string creation_error;
 
+//  Owning holders of HIP resources: destruction releases them.
+template<typename H, hipError_t (*release)(H)>
+struct releaser {
+    void operator()(H handle) const { (void)release(handle); }
+};
+template<typename T = void> using device_ptr = std::unique_ptr<T, releaser<void *, hipFree>>;
+template<typename T = void> using host_ptr = std::unique_ptr<T, releaser<void *, hipHostFree>>;       // pinned
+using module_ptr = std::unique_ptr<std::remove_pointer_t<hipModule_t>, releaser<hipModule_t, hipModuleUnload>>;
+using event_ptr = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, releaser<hipEvent_t, hipEventDestroy>>;
+using stream_ptr = std::unique_ptr<std::remove_pointer_t<hipStream_t>, releaser<hipStream_t, hipStreamDestroy>>;
+
+template<typename T>
+hipError_t allocate(device_ptr<T> &p, const size_t bytes) {
+    void *raw = nullptr;
+    const hipError_t status = hipMalloc(&raw, bytes);
+    if (status == hipSuccess) p.reset(static_cast<T *> (raw));
+    return status;
+}
+
+template<typename T>
+hipError_t allocate(host_ptr<T> &p, const size_t bytes) {
+    void *raw = nullptr;
+    const hipError_t status = hipHostMalloc(&raw, bytes, hipHostMallocDefault);
+    if (status == hipSuccess) p.reset(static_cast<T *> (raw));
+    return status;
+}
+
+struct event_pair {
+    event_ptr start, stop;
+};
+
 struct buffer {
+    device_ptr<> owned;         // null for a buffer adopted by gfhip_set_buffer, which is never freed here
     void *pointer = nullptr;
     size_t count = 0;
     uint32_t dtype = GFIR_F64;
-    bool owned = true;
-    void *mirror = nullptr;     // pinned host copy handed out by gfhip_get_host_buffer, refreshed by gfhip_wait
+    host_ptr<> mirror;          // host copy handed out by gfhip_get_host_buffer, refreshed by gfhip_wait
 };
 
 std::string library_directory() {
@@ -86,22 +119,23 @@ std::string hash_name(const uint64_t hash) {
 
 }  // namespace
 
+//  Members are released last to first: the kernels and buffers, then the owned stream.
 struct gfhip_context {
     int device = 0;
+    stream_ptr own_stream;                         // set when the context created `stream`
     hipStream_t stream = nullptr;
-    bool own_stream = false;
     unsigned int num_cus = 256;
+    device_ptr<unsigned long long> device_scalar;  // 8 words: one per pass of a batch
+    host_ptr<unsigned long long> host_scalar;      // 8 words
+    device_ptr<unsigned int> device_flags;         // bit 0: a lane redid a pass with the compiler's division
+    device_ptr<gfhip::converge_state> device_converge;
+    host_ptr<gfhip::converge_state> host_converge;
     std::map<uint64_t, buffer> buffers;
-    std::map<uint64_t, std::pair<void *, size_t>> random_states;    // MT19937 states per random_state node (raw bytes)
+    std::map<uint64_t, device_ptr<>> random_states;    // MT19937 states per random_state node (raw bytes)
     std::vector<std::unique_ptr<gfhip_kernel>> kernels;
     std::string error;
-    unsigned long long *device_scalar = nullptr;
-    unsigned long long *host_scalar = nullptr;     // pinned, 8 words
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
-    unsigned int *device_flags = nullptr;          // bit 0: a lane redid a pass with the compiler's division
-    gfhip::converge_state *device_converge = nullptr;
-    gfhip::converge_state *host_converge = nullptr;   // pinned
     unsigned int timing = 0;                       // 0 = off, N = events around every Nth launch of a kernel
 
     int fail(const std::string &message) {
@@ -116,13 +150,16 @@ struct gfhip_context {
     }
 };
 
-//  One compiled kernel of a work item: the item itself, or one segment of it (segments.hpp).
+//  One compiled kernel of a work item: the item itself, one segment of it (segments.hpp) or its redo launch.
 struct built_piece {
-    gfhip::segment plan;                           // the piece as an item, and what its symbols and outputs are
+    gfhip::segment plan;                           // a segment as an item, and what its symbols and outputs are
     gfhip::lowered low;
-    hipModule_t module = nullptr;
+    module_ptr module;
     hipFunction_t function = nullptr;
-    std::vector<void *> pack_device;
+    hipFunction_t max_function = nullptr;          // `<name>_max`
+    hipFunction_t converge_function = nullptr;     // `<name>_converge`
+    hipFunction_t batch_function = nullptr;        // `<name>_batch`: several passes per launch, one max per pass
+    std::vector<device_ptr<>> packs;
     unsigned int grid = 1;
     int vgprs = 0, lds_static = 0, scratch = 0;
     bool from_cache = false;
@@ -131,35 +168,26 @@ struct built_piece {
 struct gfhip_kernel {
     gfhip_context *ctx = nullptr;
     gfhip::item item;
-    gfhip::lowered low;
+    built_piece whole;                             // the item's kernel; of a segmented item, its name and hash and the pieces' totals
     std::vector<built_piece> pieces;               // non-empty: the item runs as this sequence of segment kernels
-    std::vector<void *> handover;                  // one device array of `chunk` elements per hand-over slot
+    std::vector<device_ptr<>> handover;            // one device array of `chunk` elements per hand-over slot
     size_t chunk = 0;                              // rays per walk of the segment sequence
-    bool has_redo = false;                         // lanes outside the division window are redone by `redo`, a launch of its own
-    built_piece redo;                              // the whole item with the compiler's division, over the redo list
-    unsigned char *flagged = nullptr;              // per ray: a segment before the last found it outside the window
-    unsigned int *redo_list = nullptr, *redo_count = nullptr;
+    std::optional<built_piece> redo;               // lanes outside the division window are redone by this launch of its own:
+                                                   // the whole item with the compiler's division, over the redo list
+    device_ptr<unsigned char> flagged;             // per ray: a segment before the last found it outside the window
+    device_ptr<unsigned int> redo_list, redo_count;
     size_t num_rays = 0;
-    hipModule_t module = nullptr;
-    hipFunction_t function = nullptr;
-    hipFunction_t converge_function = nullptr;
-    hipFunction_t max_function = nullptr;
-    hipFunction_t batch_function = nullptr;         // `<name>_batch`: several passes per launch, one max per pass
-    std::vector<void *> undo;                      // per setter: the target's values at the beginning of the last batch
+    std::vector<device_ptr<>> undo;                // per setter: the target's values at the beginning of the last batch
 //  gfhip_run_max called in a row (the reference's converge_item::run, workflow.hpp:179-205, through hip_context's
 //  create_max_call): passes of the last `<name>_batch` launch that ran ahead of the caller, their maxes waiting here.
     std::vector<double> ahead;
     unsigned int ahead_taken = 0;
     bool built = false;
-    bool from_cache = false;
-    std::vector<void *> pack_device;
     std::vector<uint64_t> input_keys, output_keys;
     void *random_states = nullptr;                 // device copy of the item's random_state node (items with draws)
     bool bound = false;
-    unsigned int grid = 1;
-    int vgprs = 0, sgprs = 0, lds_static = 0, scratch = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
+    std::vector<event_pair> events;
+    std::vector<event_pair> free_events;
     uint64_t launch_count = 0;
     std::vector<double> samples;                   // durations drained by the last gfhip_kernel_timing
 };
@@ -225,68 +253,25 @@ extern "C" gfhip_context *gfhip_create_context(int index, void *stream) {
             creation_error = std::string("hipStreamCreate: ") + hipGetErrorString(status);
             return nullptr;
         }
-        ctx->own_stream = true;
+        ctx->own_stream.reset(ctx->stream);
     }
-    if (hipMalloc(reinterpret_cast<void **> (&ctx->device_flags), sizeof(unsigned int)) != hipSuccess ||
-        hipMemset(ctx->device_flags, 0, sizeof(unsigned int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **> (&ctx->device_scalar), 8*sizeof(unsigned long long)) != hipSuccess ||     // one per pass of a batch
-        hipMemset(ctx->device_scalar, 0, 8*sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **> (&ctx->host_scalar), 8*sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **> (&ctx->device_converge), sizeof(gfhip::converge_state)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **> (&ctx->host_converge), sizeof(gfhip::converge_state), hipHostMallocDefault) != hipSuccess) {
+    if (allocate(ctx->device_flags, sizeof(unsigned int)) != hipSuccess ||
+        hipMemset(ctx->device_flags.get(), 0, sizeof(unsigned int)) != hipSuccess ||
+        allocate(ctx->device_scalar, 8*sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(ctx->device_scalar.get(), 0, 8*sizeof(unsigned long long)) != hipSuccess ||
+        allocate(ctx->host_scalar, 8*sizeof(unsigned long long)) != hipSuccess ||
+        allocate(ctx->device_converge, sizeof(gfhip::converge_state)) != hipSuccess ||
+        allocate(ctx->host_converge, sizeof(gfhip::converge_state)) != hipSuccess) {
         creation_error = "cannot allocate reduction scalars";
-        gfhip_destroy_context(ctx.release());                  // frees whatever was allocated
         return nullptr;
     }
     return ctx.release();
-}
-
-static void release_kernel(gfhip_kernel *k) {
-    for (void *p : k->pack_device) {
-        if (p) (void)hipFree(p);
-    }
-    for (auto &piece : k->pieces) {
-        for (void *p : piece.pack_device) {
-            if (p) (void)hipFree(p);
-        }
-        if (piece.module) (void)hipModuleUnload(piece.module);
-    }
-    for (void *p : k->handover) {
-        if (p) (void)hipFree(p);
-    }
-    for (void *p : k->redo.pack_device) {
-        if (p) (void)hipFree(p);
-    }
-    for (void *p : k->undo) {
-        if (p) (void)hipFree(p);
-    }
-    if (k->redo.module) (void)hipModuleUnload(k->redo.module);
-    if (k->flagged) (void)hipFree(k->flagged);
-    if (k->redo_list) (void)hipFree(k->redo_list);
-    if (k->redo_count) (void)hipFree(k->redo_count);
-    for (auto &e : k->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto &e : k->free_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    if (k->module) (void)hipModuleUnload(k->module);
 }
 
 extern "C" void gfhip_destroy_context(gfhip_context *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (auto &k : ctx->kernels) release_kernel(k.get());
-    for (auto &kv : ctx->buffers) {
-        if (kv.second.owned && kv.second.pointer) (void)hipFree(kv.second.pointer);
-        if (kv.second.mirror) (void)hipHostFree(kv.second.mirror);
-    }
-    for (auto &kv : ctx->random_states) {
-        if (kv.second.first) (void)hipFree(kv.second.first);
-    }
-    if (ctx->device_converge) (void)hipFree(ctx->device_converge);
-    if (ctx->host_converge) (void)hipHostFree(ctx->host_converge);
-    if (ctx->device_scalar) (void)hipFree(ctx->device_scalar);
-    if (ctx->device_flags) (void)hipFree(ctx->device_flags);
-    if (ctx->host_scalar) (void)hipHostFree(ctx->host_scalar);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
@@ -294,7 +279,7 @@ extern "C" void gfhip_destroy_context(gfhip_context *ctx) {
 //  more than options.segment_nodes records, or every large item when GFHIP_SEGMENTS asks for it — as a
 //  sequence of segment kernels (segments.hpp).  Returns the number of hand-over slots.
 static uint32_t plan_item(const gfhip::item &it, gfhip::lowered &whole, std::vector<built_piece> &pieces,
-                          built_piece *redo = nullptr, bool *has_redo = nullptr) {
+                          std::optional<built_piece> *redo = nullptr) {
     const gfhip::codegen_options opt = gfhip::codegen_options::from_environment();
     size_t count = 1;
     bool automatic = false;
@@ -359,16 +344,16 @@ static uint32_t plan_item(const gfhip::item &it, gfhip::lowered &whole, std::vec
         piece.plan = std::move(plan.segments[p]);
         pieces.push_back(std::move(piece));
     }
-    if (has_redo) *has_redo = with_redo;
     if (with_redo && redo) {
         gfhip::piece_info role;
         role.role = gfhip::piece_role::redo;
         gfhip::codegen_options plain = opt;
         plain.division = gfhip::division_mode::ieee;
         plain.waves_per_simd = 0;
-        redo->plan.piece = it;
-        redo->plan.piece.name = it.name + "_redo";
-        redo->low = gfhip::lower(redo->plan.piece, plain, role);
+        built_piece &r = redo->emplace();
+        r.plan.piece = it;
+        r.plan.piece.name = it.name + "_redo";
+        r.low = gfhip::lower(r.plan.piece, plain, role);
     }
     whole = gfhip::lowered();
     whole.kernel_name = "gfhip_" + it.name;
@@ -387,7 +372,7 @@ extern "C" gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, 
     if (!k->item.parse(gfir, bytes, ctx->error)) {
         return nullptr;
     }
-    const uint32_t slots = plan_item(k->item, k->low, k->pieces, &k->redo, &k->has_redo);
+    const uint32_t slots = plan_item(k->item, k->whole.low, k->pieces, &k->redo);
     if (!k->pieces.empty()) {
 //  Rays per walk of the segment sequence: the hand-over buffers of one chunk stay in the Infinity Cache.
         const gfhip::codegen_options opt = gfhip::codegen_options::from_environment();
@@ -396,7 +381,7 @@ extern "C" gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, 
         if (chunk < 16384) chunk = 16384;
         k->chunk = num_rays < chunk ? num_rays : chunk;
         if (slots == 0) k->chunk = num_rays;         // one piece (the assembly body): nothing is handed over, one walk over all rays
-        k->handover.assign(slots, nullptr);
+        k->handover.resize(slots);
     }
     ctx->kernels.push_back(std::move(k));
     return ctx->kernels.back().get();
@@ -442,16 +427,15 @@ extern "C" int gfhip_generate_piece_source(const void *gfir, size_t bytes, uint3
     }
     gfhip::lowered whole;
     std::vector<built_piece> pieces;
-    built_piece redo;
-    bool has_redo = false;
-    (void)plan_item(it, whole, pieces, &redo, &has_redo);
+    std::optional<built_piece> redo;
+    (void)plan_item(it, whole, pieces, &redo);
     const gfhip::lowered *low = nullptr;
     if (pieces.empty()) {
         if (index == 0) low = &whole;
     } else if (index < pieces.size()) {
         low = &pieces[index].low;
-    } else if (has_redo && index == pieces.size()) {
-        low = &redo.low;
+    } else if (redo && index == pieces.size()) {
+        low = &redo->low;
     }
     if (!low) return 0;                                 // past the last piece: *source stays NULL
     if (source_hash) *source_hash = low->hash;
@@ -528,52 +512,35 @@ static int load_code_object(gfhip_context *ctx, const std::string &name, const g
     return 0;
 }
 
-//  What build_module produces for one lowered item.
-struct built_module {
-    hipModule_t module = nullptr;
-    hipFunction_t function = nullptr, max_function = nullptr, converge_function = nullptr, batch_function = nullptr;
-    std::vector<void *> packs;
-    int vgprs = 0, lds_static = 0, scratch = 0;
-    bool from_cache = false;
-    unsigned int grid = 1;
-};
-
-//  Build one kernel of `rays` lanes of work per launch.  Module, functions and packs are built into
-//  `out` and handed to the caller only when every step has succeeded, so a failed build leaves
-//  nothing half-initialised behind (a later gfhip_compile retries).
-static int build_module(gfhip_context *ctx, const gfhip::item &item, const gfhip::lowered &low, const size_t rays,
-                        built_module &out) {
+//  Build one kernel of `rays` lanes of work per launch from `piece.low`.  Module, functions and packs are
+//  committed to `piece` only when every step has succeeded, so a failed build leaves it as it was (a later
+//  gfhip_compile retries).
+static int build_module(gfhip_context *ctx, const gfhip::item &item, built_piece &piece, const size_t rays) {
+    const gfhip::lowered &low = piece.low;
+    built_piece out;
     std::vector<char> code;
-    bool from_cache = false;
-    if (load_code_object(ctx, item.name, low, code, from_cache)) return 1;
+    if (load_code_object(ctx, item.name, low, code, out.from_cache)) return 1;
 
     hipModule_t module = nullptr;
-    hipFunction_t function = nullptr, max_function = nullptr, converge_function = nullptr, batch_function = nullptr;
-    std::vector<void *> packs(low.packs.size(), nullptr);
-    auto abandon = [&] (const int status) {
-        for (void *p : packs) {
-            if (p) (void)hipFree(p);
-        }
-        if (module) (void)hipModuleUnload(module);
-        return status;
-    };
-    if (ctx->check(hipModuleLoadData(&module, code.data()), "hipModuleLoadData")) return abandon(1);
-    if (ctx->check(hipModuleGetFunction(&function, module, low.kernel_name.c_str()), "hipModuleGetFunction")) return abandon(1);
-    if (low.has_max &&
-        ctx->check(hipModuleGetFunction(&max_function, module, (low.kernel_name + "_max").c_str()),
-                   "hipModuleGetFunction(max)")) return abandon(1);
-    if (low.has_converge &&
-        ctx->check(hipModuleGetFunction(&converge_function, module, (low.kernel_name + "_converge").c_str()),
-                   "hipModuleGetFunction(converge)")) return abandon(1);
-    if (low.batch > 1 &&
-        ctx->check(hipModuleGetFunction(&batch_function, module, (low.kernel_name + "_batch").c_str()),
-                   "hipModuleGetFunction(batch)")) return abandon(1);
-    int vgprs = 0, lds_static = 0, scratch = 0;
-    (void)hipFuncGetAttribute(&vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, function);
-    (void)hipFuncGetAttribute(&lds_static, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, function);
-    (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, function);
+    GFHIP_TRY(ctx, hipModuleLoadData(&module, code.data()), "hipModuleLoadData");
+    out.module.reset(module);
+    GFHIP_TRY(ctx, hipModuleGetFunction(&out.function, module, low.kernel_name.c_str()), "hipModuleGetFunction");
+    if (low.has_max) {
+        GFHIP_TRY(ctx, hipModuleGetFunction(&out.max_function, module, (low.kernel_name + "_max").c_str()), "hipModuleGetFunction(max)");
+    }
+    if (low.has_converge) {
+        GFHIP_TRY(ctx, hipModuleGetFunction(&out.converge_function, module, (low.kernel_name + "_converge").c_str()),
+                  "hipModuleGetFunction(converge)");
+    }
+    if (low.batch > 1) {
+        GFHIP_TRY(ctx, hipModuleGetFunction(&out.batch_function, module, (low.kernel_name + "_batch").c_str()),
+                  "hipModuleGetFunction(batch)");
+    }
+    (void)hipFuncGetAttribute(&out.vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, out.function);
+    (void)hipFuncGetAttribute(&out.lds_static, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, out.function);
+    (void)hipFuncGetAttribute(&out.scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, out.function);
     if (low.lds_bytes > 48*1024) {
-        for (hipFunction_t f : {function, max_function, converge_function, batch_function}) {
+        for (hipFunction_t f : {out.function, out.max_function, out.converge_function, out.batch_function}) {
             if (f) (void)hipFuncSetAttribute(reinterpret_cast<const void *> (f), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              static_cast<int> (low.lds_bytes));
         }
@@ -583,8 +550,7 @@ static int build_module(gfhip_context *ctx, const gfhip::item &item, const gfhip
     const size_t esize = item.element_size();
     const size_t parts = item.is_complex() ? 2 : 1;
     const bool wide = item.base_is_f64();
-    for (size_t p = 0; p < low.packs.size(); p++) {
-        const gfhip::pack &pk = low.packs[p];
+    for (const gfhip::pack &pk : low.packs) {
         const size_t cells = pk.cells();
         std::vector<unsigned char> host(pk.elements()*esize, 0);
         for (size_t column = 0; column < pk.tables.size(); column++) {
@@ -600,8 +566,9 @@ static int build_module(gfhip_context *ctx, const gfhip::item &item, const gfhip
                 }
             }
         }
-        if (ctx->check(hipMalloc(&packs[p], host.size() ? host.size() : 8), "hipMalloc(pack)")) return abandon(1);
-        if (ctx->check(hipMemcpy(packs[p], host.data(), host.size(), hipMemcpyHostToDevice), "hipMemcpy(pack)")) return abandon(1);
+        out.packs.emplace_back();
+        GFHIP_TRY(ctx, allocate(out.packs.back(), host.size() ? host.size() : 8), "hipMalloc(pack)");
+        GFHIP_TRY(ctx, hipMemcpy(out.packs.back().get(), host.data(), host.size(), hipMemcpyHostToDevice), "hipMemcpy(pack)");
     }
 
 //  Launch geometry: one lane per ray; the kernel grid-strides, so cap the grid
@@ -615,7 +582,7 @@ static int build_module(gfhip_context *ctx, const gfhip::item &item, const gfhip
 //  per SIMD) run best with exactly one workgroup per CU: 0.279 vs 0.298 ms per step at 1e6
 //  rays (the coefficient packs are staged into LDS once per workgroup instead of 15 times).
     int resident = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&resident, function, static_cast<int> (block),
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&resident, out.function, static_cast<int> (block),
                                                            low.lds_bytes) != hipSuccess || resident < 1) {
         resident = 1;
     }
@@ -627,107 +594,52 @@ static int build_module(gfhip_context *ctx, const gfhip::item &item, const gfhip
     if (const char *env = std::getenv("GFHIP_GRID_PER_CU")) {
         cap = static_cast<size_t> (ctx->num_cus)*static_cast<size_t> (std::atoi(env) > 0 ? std::atoi(env) : 1);
     }
-
-    out.module = module;
-    out.function = function;
-    out.max_function = max_function;
-    out.converge_function = converge_function;
-    out.batch_function = batch_function;
-    out.packs = packs;
-    out.vgprs = vgprs;
-    out.lds_static = lds_static;
-    out.scratch = scratch;
-    out.from_cache = from_cache;
     out.grid = static_cast<unsigned int> (want < cap ? want : cap);
 //  A kernel that draws random numbers: lane t owns MT19937 state t of 1024 and serves elements
 //  t, t + 1024, ... in order (cuda_context.hpp:509-522 launches one 1024-thread block per 1024
 //  elements, one after the other).
     if (item.has_random() && out.grid*block > 1024) out.grid = static_cast<unsigned int> (1024/block);
+
+//  The piece keeps its plan and lowering (`item` may be the plan's: not used past this point).
+    out.plan = std::move(piece.plan);
+    out.low = std::move(piece.low);
+    piece = std::move(out);
     return 0;
 }
 
 static int build_kernel(gfhip_context *ctx, gfhip_kernel *k) {
-    if (!k->pieces.empty()) {
-//  A segmented item: every piece is a kernel of its own over one chunk of rays; one device array
-//  per hand-over slot.  Everything is committed only when every piece has been built.
-        std::vector<built_module> modules(k->pieces.size());
-        std::vector<void *> handover(k->handover.size(), nullptr);
-        auto abandon = [&] (const int status) {
-            for (auto &m : modules) {
-                for (void *p : m.packs) {
-                    if (p) (void)hipFree(p);
-                }
-                if (m.module) (void)hipModuleUnload(m.module);
-            }
-            for (void *p : handover) {
-                if (p) (void)hipFree(p);
-            }
-            return status;
-        };
-        for (size_t p = 0; p < k->pieces.size(); p++) {
-            if (build_module(ctx, k->pieces[p].plan.piece, k->pieces[p].low, k->chunk, modules[p])) return abandon(1);
-        }
-        const size_t bytes = k->chunk*k->item.element_size();
-        for (auto &slot : handover) {
-            if (ctx->check(hipMalloc(&slot, bytes ? bytes : 8), "hipMalloc(hand-over)")) return abandon(1);
-        }
-        if (k->has_redo) {
-            built_module redo;
-            if (build_module(ctx, k->redo.plan.piece, k->redo.low, 64*256, redo)) return abandon(1);
-            const size_t rays = k->num_rays ? k->num_rays : 1;
-            if (ctx->check(hipMalloc(reinterpret_cast<void **> (&k->flagged), rays), "hipMalloc(flagged)") ||
-                ctx->check(hipMemset(k->flagged, 0, rays), "hipMemset(flagged)") ||
-                ctx->check(hipMalloc(reinterpret_cast<void **> (&k->redo_list), rays*sizeof(unsigned int)), "hipMalloc(redo list)") ||
-                ctx->check(hipMalloc(reinterpret_cast<void **> (&k->redo_count), 2*sizeof(unsigned int)), "hipMalloc(redo count)") ||
-                ctx->check(hipMemset(k->redo_count, 0, 2*sizeof(unsigned int)), "hipMemset(redo count)")) {
-                for (void *p : redo.packs) {
-                    if (p) (void)hipFree(p);
-                }
-                (void)hipModuleUnload(redo.module);
-                return abandon(1);
-            }
-            k->redo.module = redo.module;
-            k->redo.function = redo.function;
-            k->redo.pack_device = redo.packs;
-            k->redo.grid = redo.grid;
-            k->redo.vgprs = redo.vgprs;
-            k->redo.scratch = redo.scratch;
-            k->redo.from_cache = redo.from_cache;
-        }
-        for (size_t p = 0; p < k->pieces.size(); p++) {
-            built_piece &piece = k->pieces[p];
-            piece.module = modules[p].module;
-            piece.function = modules[p].function;
-            piece.pack_device = modules[p].packs;
-            piece.grid = modules[p].grid;
-            piece.vgprs = modules[p].vgprs;
-            piece.lds_static = modules[p].lds_static;
-            piece.scratch = modules[p].scratch;
-            piece.from_cache = modules[p].from_cache;
-            k->vgprs = std::max(k->vgprs, piece.vgprs);
-            k->scratch = std::max(k->scratch, piece.scratch);
-            k->lds_static = std::max(k->lds_static, piece.lds_static);
-        }
-        k->handover = handover;
-        k->from_cache = true;
-        for (auto &piece : k->pieces) k->from_cache = k->from_cache && piece.from_cache;
-        k->grid = k->pieces[0].grid;
+    if (k->pieces.empty()) {
+        if (build_module(ctx, k->item, k->whole, k->num_rays)) return 1;
         k->built = true;
         return 0;
     }
-    built_module built;
-    if (build_module(ctx, k->item, k->low, k->num_rays, built)) return 1;
-    k->module = built.module;
-    k->function = built.function;
-    k->max_function = built.max_function;
-    k->converge_function = built.converge_function;
-    k->batch_function = built.batch_function;
-    k->pack_device = built.packs;
-    k->vgprs = built.vgprs;
-    k->lds_static = built.lds_static;
-    k->scratch = built.scratch;
-    k->from_cache = built.from_cache;
-    k->grid = built.grid;
+//  A segmented item: every piece is a kernel of its own over one chunk of rays; one device array
+//  per hand-over slot.  The kernel counts as built only when every piece has been.
+    for (auto &piece : k->pieces) {
+        if (build_module(ctx, piece.plan.piece, piece, k->chunk)) return 1;
+    }
+    const size_t bytes = k->chunk*k->item.element_size();
+    for (auto &slot : k->handover) {
+        GFHIP_TRY(ctx, allocate(slot, bytes ? bytes : 8), "hipMalloc(hand-over)");
+    }
+    if (k->redo) {
+        if (build_module(ctx, k->redo->plan.piece, *k->redo, 64*256)) return 1;
+        const size_t rays = k->num_rays ? k->num_rays : 1;
+        GFHIP_TRY(ctx, allocate(k->flagged, rays), "hipMalloc(flagged)");
+        GFHIP_TRY(ctx, hipMemset(k->flagged.get(), 0, rays), "hipMemset(flagged)");
+        GFHIP_TRY(ctx, allocate(k->redo_list, rays*sizeof(unsigned int)), "hipMalloc(redo list)");
+        GFHIP_TRY(ctx, allocate(k->redo_count, 2*sizeof(unsigned int)), "hipMalloc(redo count)");
+        GFHIP_TRY(ctx, hipMemset(k->redo_count.get(), 0, 2*sizeof(unsigned int)), "hipMemset(redo count)");
+    }
+    built_piece &whole = k->whole;
+    whole.from_cache = true;
+    for (auto &piece : k->pieces) {
+        whole.vgprs = std::max(whole.vgprs, piece.vgprs);
+        whole.scratch = std::max(whole.scratch, piece.scratch);
+        whole.lds_static = std::max(whole.lds_static, piece.lds_static);
+        whole.from_cache = whole.from_cache && piece.from_cache;
+    }
+    whole.grid = k->pieces[0].grid;
     k->built = true;
     return 0;
 }
@@ -735,6 +647,21 @@ static int build_kernel(gfhip_context *ctx, gfhip_kernel *k) {
 //  Passes that ran ahead of a caller iterating on gfhip_run_max are taken back before anything else looks at the state
 //  (defined with the batch launches below).
 static int settle(gfhip_context *ctx);
+
+//  Entry points that touch the device begin here: the context's device, then the state settled.  gfhip_run_max
+//  settles only when it does not continue a streak (run_max_ahead); gfhip_compile, gfhip_allocate_buffer and
+//  gfhip_kernel_timing look at no state and set the device alone.
+static int enter(gfhip_context *ctx) {
+    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    return settle(ctx);
+}
+
+//  Whether `k` may be launched: misuse is reported before anything is enqueued.
+static int ready(gfhip_kernel *k) {
+    if (!k->built) return k->ctx->fail("kernel has not been compiled (gfhip_compile)");
+    if (!k->bound) return k->ctx->fail("kernel arguments are not bound (gfhip_create_kernel_call)");
+    return 0;
+}
 
 extern "C" int gfhip_compile(gfhip_context *ctx) {
     if (!ctx) return 1;
@@ -757,18 +684,15 @@ static int ensure_buffer(gfhip_context *ctx, const uint64_t key, const size_t co
         const size_t esize = element_bytes(dtype);
         const size_t bytes = count*esize;
         if (init_count > count) init_count = count;
-        GFHIP_TRY(ctx, hipMalloc(&b.pointer, bytes ? bytes : 8), "hipMalloc(buffer)");
+        GFHIP_TRY(ctx, allocate(b.owned, bytes ? bytes : 8), "hipMalloc(buffer)");
+        b.pointer = b.owned.get();
         if (!init || init_count < count) {
             GFHIP_TRY(ctx, hipMemset(b.pointer, 0, bytes), "hipMemset(buffer)");
         }
         if (init && init_count) {
-            const hipError_t status = hipMemcpy(b.pointer, init, init_count*esize, hipMemcpyHostToDevice);
-            if (status != hipSuccess) {
-                (void)hipFree(b.pointer);
-                return ctx->check(status, "hipMemcpy(init)");
-            }
+            GFHIP_TRY(ctx, hipMemcpy(b.pointer, init, init_count*esize, hipMemcpyHostToDevice), "hipMemcpy(init)");
         }
-        ctx->buffers[key] = b;
+        ctx->buffers[key] = std::move(b);
         return 0;
     }
     if (found->second.count < count) {
@@ -785,11 +709,8 @@ extern "C" int gfhip_create_kernel_call(gfhip_kernel *k, const uint64_t *input_k
                                         const uint64_t *output_keys) {
     if (!k) return 1;
     gfhip_context *ctx = k->ctx;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     const size_t ni = k->item.symbols.size(), no = k->item.outputs.size();
-    k->input_keys.assign(input_keys, input_keys + ni);
-    k->output_keys.assign(output_keys, output_keys + no);
     for (size_t i = 0; i < ni; i++) {
 //  An input that index nodes read (index_1D/2D_node) is a buffer of its own length.
         const size_t indexed = k->item.indexed_length(static_cast<uint32_t> (i));
@@ -819,164 +740,152 @@ extern "C" int gfhip_create_kernel_call(gfhip_kernel *k, const uint64_t *input_k
             if (input_keys[i] == input_keys[j]) return ctx->fail("two inputs share one buffer");
         }
     }
+    k->input_keys.assign(input_keys, input_keys + ni);
+    k->output_keys.assign(output_keys, output_keys + no);
     k->bound = true;
     return 0;
 }
 
-//  Launch `<name>` (reduce == nullptr) or `<name>_max` (the max of the last output is folded into
-//  *reduce; a non-null `stop` word that reads non-zero makes the launch return at once).
+//  Kernel arguments by value, in order, one 8-byte slot each (a 4-byte argument in its low half):
+//  hipModuleLaunchKernel is handed the slots' addresses and copies as many bytes from each as its argument takes.
+struct arguments {
+    std::vector<uint64_t> slots;
+    template<typename T> arguments &add(const T value) {
+        static_assert(sizeof(T) <= sizeof(uint64_t) && std::is_trivially_copyable<T>::value, "one slot per argument");
+        uint64_t slot = 0;
+        std::memcpy(&slot, &value, sizeof(T));
+        slots.push_back(slot);
+        return *this;
+    }
+};
+
+//  What every kernel of an item takes first: its inputs, its outputs, its packs, the random states (items
+//  that draw), device_flags and the number of lanes `n`.  A segment (segments.hpp) reads and writes the rays
+//  from `first` on, or the hand-over slots its plan names.
+static arguments state_arguments(gfhip_kernel *k, const built_piece &code, const unsigned long long n,
+                                 const bool segment = false, const size_t first = 0) {
+    gfhip_context *ctx = k->ctx;
+    auto state = [&] (const uint64_t key) -> void * {
+        return static_cast<char *> (ctx->buffers[key].pointer) + first*k->item.element_size();
+    };
+    arguments args;
+    if (segment) {
+        const gfhip::segment &plan = code.plan;
+        for (size_t i = 0; i < plan.piece.symbols.size(); i++) {
+            args.add(plan.symbol_state[i] >= 0 ? state(k->input_keys[plan.symbol_state[i]]) : k->handover[plan.symbol_slot[i]].get());
+        }
+        for (size_t o = 0; o < plan.piece.outputs.size(); o++) {
+            args.add(plan.output_slot[o] >= 0 ? k->handover[plan.output_slot[o]].get() : state(k->output_keys[plan.output_original[o]]));
+        }
+    } else {
+        for (auto key : k->input_keys) args.add(state(key));
+        for (auto key : k->output_keys) args.add(state(key));
+    }
+    for (auto &p : code.packs) args.add(p.get());
+    if (k->item.has_random()) args.add(k->random_states);
+    args.add(ctx->device_flags.get());
+    args.add(n);
+    return args;
+}
+
+//  One hipModuleLaunchKernel: `function` of `code` over `grid` workgroups of its block size, with its LDS bytes.
+static int enqueue(gfhip_context *ctx, const built_piece &code, hipFunction_t function, const unsigned int grid,
+                   arguments &args, const char *what) {
+    std::vector<void *> params;
+    for (auto &slot : args.slots) params.push_back(&slot);
+    return ctx->check(hipModuleLaunchKernel(function, grid, 1, 1, code.low.block_size, 1, 1, static_cast<unsigned int> (code.low.lds_bytes),
+                                            ctx->stream, params.data(), nullptr), what);
+}
+
 //  A segmented item (segments.hpp): `steps` passes, each a walk over the ensemble in chunks, each chunk
 //  through the sequence of segment kernels.  A piece's symbols are state arrays (offset to the chunk) or
 //  hand-over slots; its outputs are slots or, in the last piece, the item's outputs.  Only the last
 //  piece stores state, so a chunk's pieces all read the state of the beginning of the pass.
-static int launch_pieces(gfhip_kernel *k, const uint32_t steps) {
+static int walk_pieces(gfhip_kernel *k, const uint32_t steps) {
     gfhip_context *ctx = k->ctx;
-    const size_t esize = k->item.element_size();
     for (uint32_t step = 0; step < steps; step++) {
         for (size_t first = 0; first < k->num_rays; first += k->chunk) {
-            unsigned long long n = std::min(k->chunk, k->num_rays - first);
+            const unsigned long long n = std::min(k->chunk, k->num_rays - first);
             for (auto &piece : k->pieces) {
-                std::vector<void *> pointers;
-                for (size_t i = 0; i < piece.plan.piece.symbols.size(); i++) {
-                    if (piece.plan.symbol_state[i] >= 0) {
-                        pointers.push_back(static_cast<char *> (ctx->buffers[k->input_keys[piece.plan.symbol_state[i]]].pointer) + first*esize);
-                    } else {
-                        pointers.push_back(k->handover[piece.plan.symbol_slot[i]]);
-                    }
-                }
-                for (size_t o = 0; o < piece.plan.piece.outputs.size(); o++) {
-                    if (piece.plan.output_slot[o] >= 0) {
-                        pointers.push_back(k->handover[piece.plan.output_slot[o]]);
-                    } else {
-                        pointers.push_back(static_cast<char *> (ctx->buffers[k->output_keys[piece.plan.output_original[o]]].pointer) + first*esize);
-                    }
-                }
-                for (void *p : piece.pack_device) pointers.push_back(p);
-                pointers.push_back(ctx->device_flags);
-                unsigned int one = 1;
-                unsigned int first_ray = static_cast<unsigned int> (first);
-                unsigned char *flagged = k->flagged ? k->flagged + first : nullptr;
-                std::vector<void *> params;
-                for (auto &p : pointers) params.push_back(&p);
-                params.push_back(&n);
-                if (k->has_redo) {
-                    params.push_back(&flagged);
+                arguments args = state_arguments(k, piece, n, true, first);
+                if (k->redo) {
+                    args.add(k->flagged.get() + first);
                     if (&piece == &k->pieces.back()) {
-                        params.push_back(&k->redo_list);
-                        params.push_back(&k->redo_count);
-                        params.push_back(&first_ray);
+                        args.add(k->redo_list.get()).add(k->redo_count.get()).add(static_cast<unsigned int> (first));
                     }
                 }
-                params.push_back(&one);
+                args.add(1u);
                 const size_t want = (n + piece.low.block_size - 1)/piece.low.block_size;
                 const unsigned int grid = static_cast<unsigned int> (want < piece.grid ? want : piece.grid);
-                GFHIP_TRY(ctx, hipModuleLaunchKernel(piece.function, grid, 1, 1, piece.low.block_size, 1, 1,
-                                                     static_cast<unsigned int> (piece.low.lds_bytes), ctx->stream,
-                                                     params.data(), nullptr), "hipModuleLaunchKernel(segment)");
+                if (enqueue(ctx, piece, piece.function, grid, args, "hipModuleLaunchKernel(segment)")) return 1;
             }
         }
-        if (k->has_redo) {
+        if (k->redo) {
 //  The lanes the segments left alone: the whole item with the compiler's division, from the untouched state.
-            std::vector<void *> pointers;
-            for (auto key : k->input_keys) pointers.push_back(ctx->buffers[key].pointer);
-            for (auto key : k->output_keys) pointers.push_back(ctx->buffers[key].pointer);
-            for (void *p : k->redo.pack_device) pointers.push_back(p);
-            pointers.push_back(ctx->device_flags);
-            unsigned long long n = k->num_rays;
-            unsigned int one = 1;
-            std::vector<void *> params;
-            for (auto &p : pointers) params.push_back(&p);
-            params.push_back(&n);
-            params.push_back(&k->flagged);
-            params.push_back(&k->redo_list);
-            params.push_back(&k->redo_count);
-            params.push_back(&one);
 //  One workgroup per CU: an empty list costs the launch either way (5 us), a long one (the O-mode step on the CLI beam
 //  sends a third of its lanes here) is walked by the whole chip.
-            GFHIP_TRY(ctx, hipModuleLaunchKernel(k->redo.function, ctx->num_cus, 1, 1, k->redo.low.block_size, 1, 1,
-                                                 static_cast<unsigned int> (k->redo.low.lds_bytes), ctx->stream,
-                                                 params.data(), nullptr), "hipModuleLaunchKernel(redo)");
+            arguments args = state_arguments(k, *k->redo, k->num_rays);
+            args.add(k->flagged.get()).add(k->redo_list.get()).add(k->redo_count.get()).add(1u);
+            if (enqueue(ctx, *k->redo, k->redo->function, ctx->num_cus, args, "hipModuleLaunchKernel(redo)")) return 1;
 //  (the redo kernel leaves the count — and its arrival counter, the second word — at zero)
         }
     }
     return 0;
 }
 
-static int launch(gfhip_kernel *k, const uint32_t steps, unsigned long long *reduce = nullptr,
-                  const unsigned int *stop = nullptr) {
+//  Every launch of an item goes through here: `<name>` (`steps` passes; a segmented item walks its segment
+//  kernels and its redo launch instead), `<name>_max` (`tail`: reduce, stop — a non-null `stop` word that reads
+//  non-zero makes the launch return at once), `<name>_batch` (`tail`: reduce, stop, the undo arrays) or
+//  `<name>_converge` (`tail`: tolerance, max_iterations, counter; no `steps` argument).  A launch of no work
+//  enqueues nothing.  With `timed`, every ctx->timing-th launch of the item is bracketed by an event pair.
+static int launch(gfhip_kernel *k, const gfhip::entry which, const uint32_t steps, const arguments &tail = arguments(),
+                  const bool timed = true) {
     gfhip_context *ctx = k->ctx;
-    if (!k->built) return ctx->fail("kernel has not been compiled (gfhip_compile)");
-    if (!k->bound) return ctx->fail("kernel arguments are not bound (gfhip_create_kernel_call)");
+    if (ready(k)) return 1;
     if (k->num_rays == 0 || steps == 0) return 0;
-    if (reduce && !k->max_function) return ctx->fail("item has no in-launch max reduction");
-    if (!k->pieces.empty()) {
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        const bool timed = ctx->timing && (k->launch_count++ % ctx->timing) == 0;
-        if (timed) {
-            if (!k->free_events.empty()) {
-                ev = k->free_events.back();
-                k->free_events.pop_back();
-            } else {
-                GFHIP_TRY(ctx, hipEventCreate(&ev.first), "hipEventCreate");
-                GFHIP_TRY(ctx, hipEventCreate(&ev.second), "hipEventCreate");
-            }
-            GFHIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream), "hipEventRecord");
-        }
-        if (launch_pieces(k, steps)) return 1;
-        if (timed) {
-            GFHIP_TRY(ctx, hipEventRecord(ev.second, ctx->stream), "hipEventRecord");
-            k->events.push_back(ev);
-        }
-        return 0;
+    if (k->item.has_random() && !k->random_states) {
+        return ctx->fail("the item draws random numbers but no random state is bound (gfhip_set_random_state)");
     }
-
-    std::vector<void *> pointers;
-    for (auto key : k->input_keys) pointers.push_back(ctx->buffers[key].pointer);
-    for (auto key : k->output_keys) pointers.push_back(ctx->buffers[key].pointer);
-    for (void *p : k->pack_device) pointers.push_back(p);
-    if (k->item.has_random()) {
-        if (!k->random_states) return ctx->fail("the item draws random numbers but no random state is bound (gfhip_set_random_state)");
-        pointers.push_back(k->random_states);
-    }
-    pointers.push_back(ctx->device_flags);
-    unsigned long long n = k->num_rays;
-    unsigned int step_count = steps;
-    std::vector<void *> params;
-    for (auto &p : pointers) params.push_back(&p);
-    params.push_back(&n);
-    params.push_back(&step_count);
-    if (reduce) {
-        params.push_back(&reduce);
-        params.push_back(&stop);
-    }
-
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool timed = ctx->timing && (k->launch_count++ % ctx->timing) == 0;
-    if (timed) {
+    event_pair ev;
+    const bool time_this = timed && ctx->timing && (k->launch_count++ % ctx->timing) == 0;
+    if (time_this) {
         if (!k->free_events.empty()) {
-            ev = k->free_events.back();
+            ev = std::move(k->free_events.back());
             k->free_events.pop_back();
         } else {
-            GFHIP_TRY(ctx, hipEventCreate(&ev.first), "hipEventCreate");
-            GFHIP_TRY(ctx, hipEventCreate(&ev.second), "hipEventCreate");
+            hipEvent_t start = nullptr, stop = nullptr;
+            GFHIP_TRY(ctx, hipEventCreate(&start), "hipEventCreate");
+            ev.start.reset(start);
+            GFHIP_TRY(ctx, hipEventCreate(&stop), "hipEventCreate");
+            ev.stop.reset(stop);
         }
-        GFHIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream), "hipEventRecord");
+        GFHIP_TRY(ctx, hipEventRecord(ev.start.get(), ctx->stream), "hipEventRecord");
     }
-    GFHIP_TRY(ctx, hipModuleLaunchKernel(reduce ? k->max_function : k->function, k->grid, 1, 1, k->low.block_size, 1, 1,
-                                         static_cast<unsigned int> (k->low.lds_bytes), ctx->stream,
-                                         params.data(), nullptr), "hipModuleLaunchKernel");
-    if (timed) {
-        GFHIP_TRY(ctx, hipEventRecord(ev.second, ctx->stream), "hipEventRecord");
-        k->events.push_back(ev);
+    if (!k->pieces.empty()) {
+        if (walk_pieces(k, steps)) return 1;
+    } else {
+        const built_piece &whole = k->whole;
+        hipFunction_t function = whole.function;
+        const char *what = "hipModuleLaunchKernel";
+        if (which == gfhip::entry::max) function = whole.max_function;
+        if (which == gfhip::entry::converge) function = whole.converge_function, what = "hipModuleLaunchKernel(converge)";
+        if (which == gfhip::entry::batch) function = whole.batch_function, what = "hipModuleLaunchKernel(batch)";
+        arguments args = state_arguments(k, whole, k->num_rays);
+        if (which != gfhip::entry::converge) args.add(steps);
+        args.slots.insert(args.slots.end(), tail.slots.begin(), tail.slots.end());
+        if (enqueue(ctx, whole, function, whole.grid, args, what)) return 1;
+    }
+    if (time_this) {
+        GFHIP_TRY(ctx, hipEventRecord(ev.stop.get(), ctx->stream), "hipEventRecord");
+        k->events.push_back(std::move(ev));
     }
     return 0;
 }
 
 extern "C" int gfhip_run(gfhip_kernel *k, uint32_t steps) {
     if (!k) return 1;
-    GFHIP_TRY(k->ctx, hipSetDevice(k->ctx->device), "hipSetDevice");
-    if (settle(k->ctx)) return 1;
-    return launch(k, steps);
+    if (enter(k->ctx)) return 1;
+    return launch(k, gfhip::entry::plain, steps);
 }
 
 static double decode_ordered(const unsigned long long key, const bool f64) {
@@ -997,86 +906,85 @@ static double decode_ordered(const unsigned long long key, const bool f64) {
 //  inside the launch for items that have `<name>_max`, else the separate reduction kernel.
 static int enqueue_pass_with_max(gfhip_kernel *k, const unsigned int *stop) {
     gfhip_context *ctx = k->ctx;
-    if (k->max_function) {
-        return launch(k, 1, ctx->device_scalar, stop);
+    if (k->whole.max_function) {
+        return launch(k, gfhip::entry::max, 1, arguments().add(ctx->device_scalar.get()).add(stop));
     }
-    if (launch(k, 1)) return 1;
+    if (launch(k, gfhip::entry::plain, 1)) return 1;
     const buffer &b = ctx->buffers[k->output_keys.back()];
-    gfhip::launch_max_reduce(b.pointer, k->num_rays, k->item.dtype == GFIR_F64, ctx->device_scalar,
+    gfhip::launch_max_reduce(b.pointer, k->num_rays, k->item.dtype == GFIR_F64, ctx->device_scalar.get(),
                              ctx->num_cus, ctx->stream);
     GFHIP_TRY(ctx, hipGetLastError(), "max_reduce launch");
     return 0;
 }
 
-//  Complex items: run, then the element of largest modulus of the last output, as
-//  cpu_context.hpp:314-318 selects it (std::max_element on std::abs, the first of equals).
-extern "C" int gfhip_run_max_complex(gfhip_kernel *k, double *value) {
-    if (!k || !value) return 1;
-    gfhip_context *ctx = k->ctx;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (k->output_keys.empty()) return ctx->fail("converge item has no output to reduce");
-    if (!k->item.is_complex()) {
-        value[1] = 0.0;
-        return gfhip_run_max(k, value);
-    }
-    if (settle(ctx)) return 1;
-    if (launch(k, 1)) return 1;
-    value[0] = value[1] = 0.0;
-    if (k->num_rays == 0) return 0;
-    const buffer &b = ctx->buffers[k->output_keys.back()];
-    const bool wide = k->item.base_is_f64();
-    gfhip::launch_max_modulus(b.pointer, k->num_rays, wide, ctx->device_converge, ctx->stream);
+//  The max left in ctx->device_scalar, on the host.
+static int read_max(gfhip_context *ctx, const bool f64, double *value) {
+    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar.get(), ctx->device_scalar.get(), sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    *value = decode_ordered(*ctx->host_scalar, f64);
+    return 0;
+}
+
+//  The largest of `count` real values (reduce.hip), on the host.
+static int max_of(gfhip_context *ctx, const void *values, const size_t count, const bool f64, double *value) {
+    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
+    gfhip::launch_max_reduce(values, count, f64, ctx->device_scalar.get(), ctx->num_cus, ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "max_reduce launch");
+    return read_max(ctx, f64, value);
+}
+
+//  The element of largest modulus of `count` complex values, as cpu_context.hpp:314-318 selects it
+//  (std::max_element on std::abs, the first of equals), on the host: value[0] + i value[1].
+static int max_modulus(gfhip_context *ctx, const void *values, const size_t count, const bool wide, double *value) {
+    gfhip::launch_max_modulus(values, count, wide, ctx->device_converge.get(), ctx->stream);
     GFHIP_TRY(ctx, hipGetLastError(), "max_modulus launch");
-    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_converge, ctx->device_converge, 16, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
+    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_converge.get(), ctx->device_converge.get(), 16, hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpyAsync");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     if (wide) {
-        std::memcpy(value, ctx->host_converge, 16);
+        std::memcpy(value, ctx->host_converge.get(), 16);
     } else {
         float narrow[2];
-        std::memcpy(narrow, ctx->host_converge, 8);
+        std::memcpy(narrow, ctx->host_converge.get(), 8);
         value[0] = narrow[0];
         value[1] = narrow[1];
     }
     return 0;
 }
 
+//  Complex items: run, then the element of largest modulus of the last output.
+extern "C" int gfhip_run_max_complex(gfhip_kernel *k, double *value) {
+    if (!k || !value) return 1;
+    gfhip_context *ctx = k->ctx;
+    if (ready(k)) return 1;
+    if (k->output_keys.empty()) return ctx->fail("converge item has no output to reduce");
+    if (!k->item.is_complex()) {
+        value[1] = 0.0;
+        return gfhip_run_max(k, value);
+    }
+    if (enter(ctx) || launch(k, gfhip::entry::plain, 1)) return 1;
+    value[0] = value[1] = 0.0;
+    if (k->num_rays == 0) return 0;
+    return max_modulus(ctx, ctx->buffers[k->output_keys.back()].pointer, k->num_rays, k->item.base_is_f64(), value);
+}
+
 extern "C" int gfhip_reduce_max(gfhip_context *ctx, uint64_t key, double *value) {
     if (!ctx || !value) return 1;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     auto found = ctx->buffers.find(key);
     if (found == ctx->buffers.end()) return ctx->fail("unknown buffer key");
     const buffer &b = found->second;
     const bool wide = b.dtype == GFIR_F64 || b.dtype == GFIR_C64;
     value[0] = value[1] = 0.0;
     if (b.dtype == GFIR_C32 || b.dtype == GFIR_C64) {
-        if (b.count == 0) return 0;
-        gfhip::launch_max_modulus(b.pointer, b.count, wide, ctx->device_converge, ctx->stream);
-        GFHIP_TRY(ctx, hipGetLastError(), "max_modulus launch");
-        GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_converge, ctx->device_converge, 16, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
-        GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        if (wide) {
-            std::memcpy(value, ctx->host_converge, 16);
-        } else {
-            float narrow[2];
-            std::memcpy(narrow, ctx->host_converge, 8);
-            value[0] = narrow[0];
-            value[1] = narrow[1];
-        }
-        return 0;
+        return b.count ? max_modulus(ctx, b.pointer, b.count, wide, value) : 0;
     }
     if (b.count == 0) {
         value[0] = -std::numeric_limits<double>::infinity();
         return 0;
     }
-    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
-    gfhip::launch_max_reduce(b.pointer, b.count, wide, ctx->device_scalar, ctx->num_cus, ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "max_reduce launch");
-    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar, ctx->device_scalar, sizeof(unsigned long long),
-                                  hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    value[0] = decode_ordered(*ctx->host_scalar, wide);
-    return 0;
+    return max_of(ctx, b.pointer, b.count, wide, value);
 }
 
 static int run_max_ahead(gfhip_kernel *k, double *max_value, bool &answered);
@@ -1085,18 +993,17 @@ extern "C" int gfhip_run_max(gfhip_kernel *k, double *max_value) {
     if (!k) return 1;
     gfhip_context *ctx = k->ctx;
     GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (ready(k)) return 1;
     if (k->output_keys.empty()) return ctx->fail("converge item has no output to reduce");
     if (k->item.is_complex()) return ctx->fail("complex item: use gfhip_run_max_complex");
     bool answered = false;
     if (run_max_ahead(k, max_value, answered)) return 1;
-    if (answered) return 0;
-    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
-    if (enqueue_pass_with_max(k, nullptr)) return 1;
-    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar, ctx->device_scalar, sizeof(unsigned long long),
-                                  hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    *max_value = k->num_rays ? decode_ordered(*ctx->host_scalar, k->item.dtype == GFIR_F64)
-                             : -std::numeric_limits<double>::infinity();
+    if (!answered) {
+        GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
+        if (enqueue_pass_with_max(k, nullptr) || read_max(ctx, k->item.dtype == GFIR_F64, max_value)) return 1;
+        if (k->num_rays == 0) *max_value = -std::numeric_limits<double>::infinity();
+    }
+    ctx->max_streak = k;
     return 0;
 }
 
@@ -1157,94 +1064,32 @@ static int converge_loop_complex(gfhip_kernel *k, const double tolerance_, const
     return 0;
 }
 
-//  The same loop with its test on the device (reduce.hip: converge_decide_kernel): passes are
-//  enqueued ahead of the host in growing batches, each followed by the one-thread test; once
-//  the test has come out false the passes still queued return at once (`stop`), so exactly the
-//  passes of the host loop run, with the same iteration count — and the host synchronises once
-//  per batch (twice for the benchmark's 25 passes) instead of once per pass.
-static int converge_on_device(gfhip_kernel *k, const double tolerance, const size_t max_iterations,
-                              size_t *iterations_out, double *last_max) {
-    gfhip_context *ctx = k->ctx;
-    const bool f64 = k->item.dtype == GFIR_F64;
-    gfhip::converge_state &host = *ctx->host_converge;
-    host = gfhip::converge_state();
-    host.last = host.off_last = f64 ? std::numeric_limits<double>::max()
-                                    : static_cast<double> (std::numeric_limits<float>::max());
-    host.tolerance = tolerance;
-    host.limit = max_iterations;
-    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->device_converge, &host, sizeof(host), hipMemcpyHostToDevice, ctx->stream),
-              "hipMemcpyAsync(converge state)");
-    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");     // `host` is written again below
-    const unsigned int *stop = &ctx->device_converge->done;
-    const uint64_t first_launch = k->launch_count;
-    const size_t events_before = k->events.size();
-    size_t batch = 16;
-    for (;;) {
-        for (size_t p = 0; p < batch; p++) {
-            if (enqueue_pass_with_max(k, stop)) return 1;
-            gfhip::launch_converge_decide(f64, ctx->device_scalar, ctx->device_converge, ctx->stream);
-            GFHIP_TRY(ctx, hipGetLastError(), "converge_decide launch");
-        }
-        GFHIP_TRY(ctx, hipMemcpyAsync(&host, ctx->device_converge, sizeof(host), hipMemcpyDeviceToHost, ctx->stream),
-                  "hipMemcpyAsync(converge state)");
-        GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        if (host.done) break;
-        if (batch < 64) batch *= 2;
-    }
-//  Launch timing: keep the event pairs of the passes that ran (the first `passes` launches of the
-//  loop); the queued launches that returned at once are not launches of the item's work.
-    if (ctx->timing) {
-        size_t ran = 0;
-        for (uint64_t l = first_launch; l < first_launch + host.passes; l++) {
-            if (l % ctx->timing == 0) ran++;
-        }
-        while (k->events.size() > events_before + ran) {
-            k->free_events.push_back(k->events.back());
-            k->events.pop_back();
-        }
-    }
-    if (iterations_out) *iterations_out = static_cast<size_t> (host.iterations);
-    if (last_max) *last_max = host.max_residual;
-    return 0;
-}
-
 //  One launch of `<name>_batch`: `passes` passes on state kept in registers, the max of each pass folded
 //  into reduce[pass]; the setter targets as they were before the launch are saved in the undo arrays.
 static int launch_batch(gfhip_kernel *k, const unsigned int passes, const unsigned int *stop) {
-    gfhip_context *ctx = k->ctx;
-    std::vector<void *> pointers;
-    for (auto key : k->input_keys) pointers.push_back(ctx->buffers[key].pointer);
-    for (auto key : k->output_keys) pointers.push_back(ctx->buffers[key].pointer);
-    for (void *p : k->pack_device) pointers.push_back(p);
-    pointers.push_back(ctx->device_flags);
-    unsigned long long n = k->num_rays;
-    unsigned int count = passes;
-    std::vector<void *> params;
-    for (auto &p : pointers) params.push_back(&p);
-    params.push_back(&n);
-    params.push_back(&count);
-    params.push_back(&ctx->device_scalar);
-    params.push_back(&stop);
-    for (auto &u : k->undo) params.push_back(&u);
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool timed = ctx->timing && (k->launch_count++ % ctx->timing) == 0;
-    if (timed) {
-        if (!k->free_events.empty()) {
-            ev = k->free_events.back();
-            k->free_events.pop_back();
-        } else {
-            GFHIP_TRY(ctx, hipEventCreate(&ev.first), "hipEventCreate");
-            GFHIP_TRY(ctx, hipEventCreate(&ev.second), "hipEventCreate");
-        }
-        GFHIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream), "hipEventRecord");
+    arguments tail;
+    tail.add(k->ctx->device_scalar.get()).add(stop);
+    for (auto &u : k->undo) tail.add(u.get());
+    return launch(k, gfhip::entry::batch, passes, tail);
+}
+
+static int ensure_undo(gfhip_kernel *k) {
+    if (!k->undo.empty()) return 0;
+    std::vector<device_ptr<>> undo(k->item.setters.size());
+    for (auto &u : undo) {
+        GFHIP_TRY(k->ctx, allocate(u, k->num_rays*k->item.element_size()), "hipMalloc(undo)");
     }
-    GFHIP_TRY(ctx, hipModuleLaunchKernel(k->batch_function, k->grid, 1, 1, k->low.block_size, 1, 1,
-                                         static_cast<unsigned int> (k->low.lds_bytes), ctx->stream,
-                                         params.data(), nullptr), "hipModuleLaunchKernel(batch)");
-    if (timed) {
-        GFHIP_TRY(ctx, hipEventRecord(ev.second, ctx->stream), "hipEventRecord");
-        k->events.push_back(ev);
+    k->undo = std::move(undo);
+    return 0;
+}
+
+//  Back to the state of the beginning of the last batch.
+static int restore_undo(gfhip_kernel *k) {
+    gfhip_context *ctx = k->ctx;
+    for (size_t s = 0; s < k->item.setters.size(); s++) {
+        void *target = ctx->buffers[k->input_keys[k->item.setters[s].input]].pointer;
+        GFHIP_TRY(ctx, hipMemcpyAsync(target, k->undo[s].get(), k->num_rays*k->item.element_size(), hipMemcpyDeviceToDevice,
+                                      ctx->stream), "hipMemcpyAsync(undo)");
     }
     return 0;
 }
@@ -1265,12 +1110,7 @@ static int settle(gfhip_context *ctx) {
     k->ahead.clear();
     k->ahead_taken = 0;
     if (asked == ran) return 0;
-    const size_t esize = k->item.element_size();
-    for (size_t s = 0; s < k->item.setters.size(); s++) {
-        void *target = ctx->buffers[k->input_keys[k->item.setters[s].input]].pointer;
-        GFHIP_TRY(ctx, hipMemcpyAsync(target, k->undo[s], k->num_rays*esize, hipMemcpyDeviceToDevice, ctx->stream),
-                  "hipMemcpyAsync(undo)");
-    }
+    if (restore_undo(k)) return 1;
     return launch_batch(k, asked, nullptr);
 }
 
@@ -1284,32 +1124,17 @@ static int run_max_ahead(gfhip_kernel *k, double *max_value, bool &answered) {
         return 0;
     }
     const bool streak = ctx->max_streak == k;
-    if (ctx->running_ahead == k) {
-//  every pass of the last batch was asked for: nothing to take back
-        ctx->running_ahead = nullptr;
-        k->ahead.clear();
-        k->ahead_taken = 0;
-    } else if (settle(ctx)) {
-        return 1;
-    }
-    ctx->max_streak = k;
-    if (!enabled || !streak || !k->batch_function || k->num_rays == 0 || k->low.batch < 2) return 0;
-    if (k->undo.empty()) {
-        const size_t esize = k->item.element_size();
-        for (size_t s = 0; s < k->item.setters.size(); s++) {
-            void *p = nullptr;
-            GFHIP_TRY(ctx, hipMalloc(&p, k->num_rays*esize), "hipMalloc(undo)");
-            k->undo.push_back(p);
-        }
-    }
-    const unsigned int batch = std::min(k->low.batch, 8u);
-    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, 8*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
+    if (settle(ctx)) return 1;                     // nothing to take back if every pass of k's last batch was asked for
+    if (!enabled || !streak || !k->whole.batch_function || k->num_rays == 0 || k->whole.low.batch < 2) return 0;
+    if (ensure_undo(k)) return 1;
+    const unsigned int batch = std::min(k->whole.low.batch, 8u);
+    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, 8*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
     if (launch_batch(k, batch, nullptr)) return 1;
-    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar, ctx->device_scalar, batch*sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                  ctx->stream), "hipMemcpyAsync");
+    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar.get(), ctx->device_scalar.get(), batch*sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     k->ahead.clear();
-    for (unsigned int b = 0; b < batch; b++) k->ahead.push_back(decode_ordered(ctx->host_scalar[b], k->item.dtype == GFIR_F64));
+    for (unsigned int b = 0; b < batch; b++) k->ahead.push_back(decode_ordered(ctx->host_scalar.get()[b], k->item.dtype == GFIR_F64));
     k->ahead_taken = 1;
     ctx->running_ahead = k;
     *max_value = k->ahead[0];
@@ -1317,75 +1142,76 @@ static int run_max_ahead(gfhip_kernel *k, double *max_value, bool &answered) {
     return 0;
 }
 
-//  The converge loop with several passes per launch (`<name>_batch`, codegen.hpp).  A pass of this loop
+//  The same loop with its test on the device (reduce.hip: converge_decide_kernel): passes are
+//  enqueued ahead of the host in growing batches, each followed by the one-thread test; once
+//  the test has come out false the passes still queued return at once (`stop`), so exactly the
+//  passes of the host loop run, with the same iteration count — and the host synchronises once
+//  per batch (twice for the benchmark's 25 passes) instead of once per pass.
+//
+//  Items with `<name>_batch` (codegen.hpp) run several passes per launch.  A pass of this loop
 //  only feeds the next pass of the same ray and the max the loop's test looks at, so a launch may run a
 //  few passes on state kept in registers — each pass leaving its own max — and the test (on the device,
 //  reduce.hip: converge_decide_batch_kernel) is applied to those maxima in order afterwards.  If the loop
 //  turns out to have ended before the last pass of a batch, the state of the beginning of that batch is
 //  restored from the undo arrays and the batch is redone with exactly the passes the loop ran: the same
 //  passes, iteration count, state and output as one launch per pass, at a third of the sweeps over the
-//  state.  Batches are queued ahead of the host like the single passes of converge_on_device.
-static int converge_batched(gfhip_kernel *k, const double tolerance, const size_t max_iterations,
-                            size_t *iterations_out, double *last_max) {
+//  state.
+static int converge_on_device(gfhip_kernel *k, const double tolerance, const size_t max_iterations,
+                              size_t *iterations_out, double *last_max) {
     gfhip_context *ctx = k->ctx;
     const bool f64 = k->item.dtype == GFIR_F64;
-    const size_t esize = k->item.element_size();
-    const unsigned int batch = k->low.batch;
-    if (k->undo.empty()) {
-        for (size_t s = 0; s < k->item.setters.size(); s++) {
-            void *p = nullptr;
-            GFHIP_TRY(ctx, hipMalloc(&p, k->num_rays*esize), "hipMalloc(undo)");
-            k->undo.push_back(p);
-        }
-    }
+    const unsigned int batch = k->whole.batch_function ? k->whole.low.batch : 1;        // passes per launch
+    if (batch > 1 && ensure_undo(k)) return 1;
+    const size_t reduce_words = batch > 1 ? 8 : 1;
     gfhip::converge_state &host = *ctx->host_converge;
     host = gfhip::converge_state();
     host.last = host.off_last = f64 ? std::numeric_limits<double>::max()
                                     : static_cast<double> (std::numeric_limits<float>::max());
     host.tolerance = tolerance;
     host.limit = max_iterations;
-    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->device_converge, &host, sizeof(host), hipMemcpyHostToDevice, ctx->stream),
+    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->device_converge.get(), &host, sizeof(host), hipMemcpyHostToDevice, ctx->stream),
               "hipMemcpyAsync(converge state)");
-    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, 8*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
+    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, reduce_words*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");     // `host` is written again below
     const unsigned int *stop = &ctx->device_converge->done;
     const uint64_t first_launch = k->launch_count;
     const size_t events_before = k->events.size();
-    size_t queued = 6;                                     // batches per host synchronisation, growing
+    size_t queued = batch > 1 ? 6 : 16;                    // launches per host synchronisation, growing
+    const size_t most = batch > 1 ? 24 : 64;
     for (;;) {
-        for (size_t b = 0; b < queued; b++) {
-            if (launch_batch(k, batch, stop)) return 1;
-            gfhip::launch_converge_decide_batch(f64, ctx->device_scalar, ctx->device_converge, batch, ctx->stream);
+        for (size_t q = 0; q < queued; q++) {
+            if (batch > 1) {
+                if (launch_batch(k, batch, stop)) return 1;
+                gfhip::launch_converge_decide_batch(f64, ctx->device_scalar.get(), ctx->device_converge.get(), batch, ctx->stream);
+            } else {
+                if (enqueue_pass_with_max(k, stop)) return 1;
+                gfhip::launch_converge_decide(f64, ctx->device_scalar.get(), ctx->device_converge.get(), ctx->stream);
+            }
             GFHIP_TRY(ctx, hipGetLastError(), "converge_decide launch");
         }
-        GFHIP_TRY(ctx, hipMemcpyAsync(&host, ctx->device_converge, sizeof(host), hipMemcpyDeviceToHost, ctx->stream),
+        GFHIP_TRY(ctx, hipMemcpyAsync(&host, ctx->device_converge.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream),
                   "hipMemcpyAsync(converge state)");
         GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
         if (host.done) break;
-        if (queued < 24) queued *= 2;
+        if (queued < most) queued *= 2;
     }
-//  Launch timing: keep the event pairs of the batches that ran; the queued launches that returned at once
+//  Launch timing: keep the event pairs of the launches that ran; the queued launches that returned at once
 //  are not launches of the item's work.
     if (ctx->timing) {
-        const uint64_t batches = (static_cast<uint64_t> (host.passes) + host.extra + batch - 1)/batch;
-        size_t ran = 0;
-        for (uint64_t l = first_launch; l < first_launch + batches; l++) {
-            if (l % ctx->timing == 0) ran++;
+        const uint64_t ran = (static_cast<uint64_t> (host.passes) + host.extra + batch - 1)/batch;
+        size_t kept = 0;
+        for (uint64_t l = first_launch; l < first_launch + ran; l++) {
+            if (l % ctx->timing == 0) kept++;
         }
-        while (k->events.size() > events_before + ran) {
-            k->free_events.push_back(k->events.back());
+        while (k->events.size() > events_before + kept) {
+            k->free_events.push_back(std::move(k->events.back()));
             k->events.pop_back();
         }
     }
     if (host.extra) {
 //  The loop ended inside the last batch: back to the state of its beginning, then only the loop's passes.
-        for (size_t s = 0; s < k->item.setters.size(); s++) {
-            void *target = ctx->buffers[k->input_keys[k->item.setters[s].input]].pointer;
-            GFHIP_TRY(ctx, hipMemcpyAsync(target, k->undo[s], k->num_rays*esize, hipMemcpyDeviceToDevice, ctx->stream),
-                      "hipMemcpyAsync(undo)");
-        }
-        if (launch_batch(k, host.batch_passes, nullptr)) return 1;
-        GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, 8*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
+        if (restore_undo(k) || launch_batch(k, host.batch_passes, nullptr)) return 1;
+        GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, 8*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
         GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     }
     if (iterations_out) *iterations_out = static_cast<size_t> (host.iterations);
@@ -1397,20 +1223,15 @@ extern "C" int gfhip_converge(gfhip_kernel *k, double tolerance, size_t max_iter
                               size_t *iterations, double *last_max) {
     if (!k) return 1;
     gfhip_context *ctx = k->ctx;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (enter(ctx) || ready(k)) return 1;
     if (k->output_keys.empty()) return ctx->fail("converge item has no output to reduce");
-    if (settle(ctx)) return 1;
-    if (!k->built) return ctx->fail("kernel has not been compiled (gfhip_compile)");
-    if (!k->bound) return ctx->fail("kernel arguments are not bound (gfhip_create_kernel_call)");
     size_t used = 0;
     double residual = 0.0;
     int status;
     if (k->item.is_complex()) {
         status = k->item.base_is_f64() ? converge_loop_complex<double> (k, tolerance, max_iterations, &used, &residual)
                                        : converge_loop_complex<float> (k, tolerance, max_iterations, &used, &residual);
-    } else if (k->batch_function && k->num_rays > 0) {
-        status = converge_batched(k, tolerance, max_iterations, &used, &residual);
-    } else if (k->max_function && k->num_rays > 0) {
+    } else if (k->whole.max_function && k->num_rays > 0) {             // (every item with `<name>_batch` has `<name>_max`)
         status = converge_on_device(k, tolerance, max_iterations, &used, &residual);
     } else if (k->item.dtype == GFIR_F64) {
         status = converge_loop<double> (k, tolerance, max_iterations, &used, &residual);
@@ -1432,66 +1253,43 @@ extern "C" int gfhip_converge_per_ray(gfhip_kernel *k, double tolerance, size_t 
                                       size_t *iterations, double *last_max) {
     if (!k) return 1;
     gfhip_context *ctx = k->ctx;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
-    if (!k->built) return ctx->fail("kernel has not been compiled (gfhip_compile)");
-    if (!k->converge_function) return ctx->fail("item has no setter/output to converge on");
-    if (!k->bound) return ctx->fail("kernel arguments are not bound (gfhip_create_kernel_call)");
+    if (enter(ctx)) return 1;
+    if (k->built && !k->whole.converge_function) return ctx->fail("item has no setter/output to converge on");
+    if (ready(k)) return 1;
     if (k->num_rays == 0) {
         if (iterations) *iterations = 0;
         if (last_max) *last_max = -std::numeric_limits<double>::infinity();
         return 0;
     }
-    std::vector<void *> pointers;
-    for (auto key : k->input_keys) pointers.push_back(ctx->buffers[key].pointer);
-    for (auto key : k->output_keys) pointers.push_back(ctx->buffers[key].pointer);
-    for (void *p : k->pack_device) pointers.push_back(p);
-    pointers.push_back(ctx->device_flags);
-    unsigned long long n = k->num_rays;
-    double tolerance64 = tolerance;
-    float tolerance32 = static_cast<float> (tolerance);
-    unsigned int maximum = static_cast<unsigned int> (max_iterations > 0xFFFFFFFEull ? 0xFFFFFFFEull : max_iterations);
+    const bool f64 = k->item.dtype == GFIR_F64;
+    arguments tail;
+    if (f64) {
+        tail.add(tolerance);
+    } else {
+        tail.add(static_cast<float> (tolerance));
+    }
+    tail.add(static_cast<unsigned int> (max_iterations > 0xFFFFFFFEull ? 0xFFFFFFFEull : max_iterations));
 //  The iteration counter shares the 8-byte reduction scalar (low word).
-    unsigned int *counter = reinterpret_cast<unsigned int *> (ctx->device_scalar);
-    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
-    std::vector<void *> params;
-    for (auto &p : pointers) params.push_back(&p);
-    params.push_back(&n);
-    params.push_back(k->item.dtype == GFIR_F64 ? static_cast<void *> (&tolerance64) : static_cast<void *> (&tolerance32));
-    params.push_back(&maximum);
-    params.push_back(&counter);
-    GFHIP_TRY(ctx, hipModuleLaunchKernel(k->converge_function, k->grid, 1, 1, k->low.block_size, 1, 1,
-                                         static_cast<unsigned int> (k->low.lds_bytes), ctx->stream,
-                                         params.data(), nullptr), "hipModuleLaunchKernel(converge)");
-    unsigned int used = 0;
-    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar, ctx->device_scalar, sizeof(unsigned long long),
+    tail.add(reinterpret_cast<unsigned int *> (ctx->device_scalar.get()));
+    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
+    if (launch(k, gfhip::entry::converge, 1, tail, false)) return 1;
+    GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar.get(), ctx->device_scalar.get(), sizeof(unsigned long long),
                                   hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    used = static_cast<unsigned int> (*ctx->host_scalar & 0xFFFFFFFFull);
-    if (iterations) *iterations = used;
-    if (last_max) {
-        const buffer &b = ctx->buffers[k->output_keys.back()];
-        GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar, 0, sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
-        gfhip::launch_max_reduce(b.pointer, k->num_rays, k->item.dtype == GFIR_F64, ctx->device_scalar,
-                                 ctx->num_cus, ctx->stream);
-        GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar, ctx->device_scalar, sizeof(unsigned long long),
-                                      hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
-        GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        *last_max = decode_ordered(*ctx->host_scalar, k->item.dtype == GFIR_F64);
-    }
+    if (iterations) *iterations = static_cast<unsigned int> (*ctx->host_scalar & 0xFFFFFFFFull);
+    if (last_max) return max_of(ctx, ctx->buffers[k->output_keys.back()].pointer, k->num_rays, f64, last_max);
     return 0;
 }
 
 extern "C" int gfhip_wait(gfhip_context *ctx) {
     if (!ctx) return 1;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
 //  Host mirrors handed out by gfhip_get_host_buffer hold the device contents as of this drain:
 //  all copies are queued behind the kernels, then ONE synchronisation.
     for (auto &kv : ctx->buffers) {
         buffer &b = kv.second;
         if (b.mirror && b.count) {
-            GFHIP_TRY(ctx, hipMemcpyAsync(b.mirror, b.pointer, b.count*element_bytes(b.dtype),
+            GFHIP_TRY(ctx, hipMemcpyAsync(b.mirror.get(), b.pointer, b.count*element_bytes(b.dtype),
                                           hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(mirror)");
         }
     }
@@ -1501,10 +1299,9 @@ extern "C" int gfhip_wait(gfhip_context *ctx) {
 
 extern "C" int gfhip_get_flags(gfhip_context *ctx, unsigned int *flags) {
     if (!ctx || !flags) return 1;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    GFHIP_TRY(ctx, hipMemcpy(flags, ctx->device_flags, sizeof(unsigned int), hipMemcpyDeviceToHost), "hipMemcpy(flags)");
+    GFHIP_TRY(ctx, hipMemcpy(flags, ctx->device_flags.get(), sizeof(unsigned int), hipMemcpyDeviceToHost), "hipMemcpy(flags)");
     return 0;
 }
 
@@ -1521,8 +1318,7 @@ extern "C" int gfhip_copy_to_device(gfhip_context *ctx, uint64_t key, const void
     if (!ctx) return 1;
     buffer *b = find_buffer(ctx, key);
     if (!b) return 1;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     GFHIP_TRY(ctx, hipMemcpyAsync(b->pointer, host, b->count*element_bytes(b->dtype),
                                   hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(H2D)");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
@@ -1533,8 +1329,7 @@ extern "C" int gfhip_copy_to_host(gfhip_context *ctx, uint64_t key, void *host) 
     if (!ctx) return 1;
     buffer *b = find_buffer(ctx, key);
     if (!b) return 1;
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     GFHIP_TRY(ctx, hipMemcpyAsync(host, b->pointer, b->count*element_bytes(b->dtype),
                                   hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(D2H)");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
@@ -1546,8 +1341,7 @@ extern "C" int gfhip_read_element(gfhip_context *ctx, uint64_t key, size_t index
     buffer *b = find_buffer(ctx, key);
     if (!b) return 1;
     if (index >= b->count) return ctx->fail("index out of range");
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     const size_t esize = element_bytes(b->dtype);
     GFHIP_TRY(ctx, hipMemcpy(element, static_cast<char *> (b->pointer) + index*esize, esize, hipMemcpyDeviceToHost), "hipMemcpy");
@@ -1573,20 +1367,15 @@ extern "C" int gfhip_set_random_state(gfhip_kernel *k, uint64_t key, const void 
 //  The kernel indexes 1024 states of 2500 bytes (random.hpp:44-52 without the CUDA padding).
     const size_t needed = 1024*2500;
     if (!states || bytes < needed) return ctx->fail("a random state of 1024 MT19937 states (2500 bytes each) is required");
-    GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     auto found = ctx->random_states.find(key);
     if (found == ctx->random_states.end()) {
-        void *device = nullptr;
-        GFHIP_TRY(ctx, hipMalloc(&device, bytes), "hipMalloc(random state)");
-        const hipError_t status = hipMemcpy(device, states, bytes, hipMemcpyHostToDevice);
-        if (status != hipSuccess) {
-            (void)hipFree(device);
-            return ctx->check(status, "hipMemcpy(random state)");
-        }
-        found = ctx->random_states.insert({key, {device, bytes}}).first;
+        device_ptr<> device;
+        GFHIP_TRY(ctx, allocate(device, bytes), "hipMalloc(random state)");
+        GFHIP_TRY(ctx, hipMemcpy(device.get(), states, bytes, hipMemcpyHostToDevice), "hipMemcpy(random state)");
+        found = ctx->random_states.emplace(key, std::move(device)).first;
     }
-    k->random_states = found->second.first;
+    k->random_states = found->second.get();
     return 0;
 }
 
@@ -1594,7 +1383,7 @@ extern "C" void *gfhip_get_buffer(gfhip_context *ctx, uint64_t key, size_t *coun
     if (!ctx) return nullptr;
     buffer *b = find_buffer(ctx, key);
     if (!b) return nullptr;
-    if (hipSetDevice(ctx->device) != hipSuccess || settle(ctx)) return nullptr;      // the caller is about to look at the device buffer
+    if (enter(ctx)) return nullptr;            // the caller is about to look at the device buffer
     if (count) *count = b->count;
     return b->pointer;
 }
@@ -1619,38 +1408,29 @@ extern "C" void *gfhip_get_host_buffer(gfhip_context *ctx, uint64_t key, size_t 
     if (!ctx) return nullptr;
     buffer *b = find_buffer(ctx, key);
     if (!b) return nullptr;
-    if (hipSetDevice(ctx->device) != hipSuccess || settle(ctx)) return nullptr;
+    if (enter(ctx)) return nullptr;
     const size_t bytes = b->count*element_bytes(b->dtype);
     if (!b->mirror) {
-        if (ctx->check(hipHostMalloc(&b->mirror, bytes ? bytes : 8, hipHostMallocDefault), "hipHostMalloc(mirror)")) {
-            b->mirror = nullptr;
-            return nullptr;
-        }
-        if (ctx->check(hipMemcpyAsync(b->mirror, b->pointer, bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(mirror)") ||
+        if (ctx->check(allocate(b->mirror, bytes ? bytes : 8), "hipHostMalloc(mirror)") ||
+            ctx->check(hipMemcpyAsync(b->mirror.get(), b->pointer, bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(mirror)") ||
             ctx->check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
             return nullptr;
         }
     }
     if (count) *count = b->count;
-    return b->mirror;
+    return b->mirror.get();
 }
 
 extern "C" int gfhip_set_buffer(gfhip_context *ctx, uint64_t key, void *device_pointer, size_t count, uint32_t dtype) {
     if (!ctx) return 1;
-    if (settle(ctx)) return 1;
+    if (enter(ctx)) return 1;
     if (!device_pointer && count) return ctx->fail("null device pointer");
     if (dtype > GFIR_C64) return ctx->fail("bad dtype");
-    auto found = ctx->buffers.find(key);
-    if (found != ctx->buffers.end()) {
-        if (found->second.owned && found->second.pointer) (void)hipFree(found->second.pointer);
-        if (found->second.mirror) (void)hipHostFree(found->second.mirror);
-    }
-    buffer b;
+    buffer &b = ctx->buffers[key];
+    b = buffer();                                  // frees what an earlier buffer of this key owned
     b.pointer = device_pointer;
     b.count = count;
     b.dtype = dtype;
-    b.owned = false;
-    ctx->buffers[key] = b;
     return 0;
 }
 
@@ -1663,18 +1443,19 @@ extern "C" int gfhip_kernel_get_info(const gfhip_kernel *k, struct gfhip_kernel_
     info->num_setters = static_cast<uint32_t> (k->item.setters.size());
     info->num_tables = static_cast<uint32_t> (k->item.tables.size());
     info->num_instructions = static_cast<uint32_t> (k->item.code.size());
-    info->vgprs = static_cast<uint32_t> (k->vgprs);
-    size_t lds = k->low.lds_bytes;
+    const built_piece &whole = k->whole;
+    info->vgprs = static_cast<uint32_t> (whole.vgprs);
+    size_t lds = whole.low.lds_bytes;
     for (auto &piece : k->pieces) lds = std::max(lds, piece.low.lds_bytes);
-    info->lds_bytes = static_cast<uint32_t> (k->lds_static + lds);
-    info->segments = static_cast<uint32_t> (k->pieces.size());
-    info->converge_batch = k->batch_function ? k->low.batch : 0;          // segments the item runs as (0: one kernel)
-    info->scratch_bytes = static_cast<uint32_t> (k->scratch);
-    info->block_size = k->low.block_size;
-    info->grid_size = k->grid;
-    info->from_cache = k->from_cache ? 1 : 0;
-    info->source_hash = k->low.hash;
-    std::strncpy(info->name, k->low.kernel_name.c_str(), sizeof(info->name) - 1);
+    info->lds_bytes = static_cast<uint32_t> (whole.lds_static + lds);
+    info->segments = static_cast<uint32_t> (k->pieces.size());          // segments the item runs as (0: one kernel)
+    info->converge_batch = whole.batch_function ? whole.low.batch : 0;
+    info->scratch_bytes = static_cast<uint32_t> (whole.scratch);
+    info->block_size = whole.low.block_size;
+    info->grid_size = whole.grid;
+    info->from_cache = whole.from_cache ? 1 : 0;
+    info->source_hash = whole.low.hash;
+    std::strncpy(info->name, whole.low.kernel_name.c_str(), sizeof(info->name) - 1);
     return 0;
 }
 
@@ -1693,13 +1474,13 @@ extern "C" int gfhip_kernel_timing(gfhip_kernel *k, double *average_ms, uint64_t
     k->samples.clear();
     for (auto &e : k->events) {
         float ms = 0.0f;
-        GFHIP_TRY(ctx, hipEventElapsedTime(&ms, e.first, e.second), "hipEventElapsedTime");
+        GFHIP_TRY(ctx, hipEventElapsedTime(&ms, e.start.get(), e.stop.get()), "hipEventElapsedTime");
         total += ms;
         k->samples.push_back(ms);
-        k->free_events.push_back(e);
     }
     if (launches) *launches = k->events.size();
     if (average_ms) *average_ms = k->events.empty() ? 0.0 : total/static_cast<double> (k->events.size());
+    for (auto &e : k->events) k->free_events.push_back(std::move(e));
     k->events.clear();
     return 0;
 }
