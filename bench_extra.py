@@ -2,7 +2,7 @@
 """Secondary measurements (not the driver's contract; bench.py is): the other items of the hot
 path at BASELINE.json's sizes, each with HIP-event kernel time and its HBM-roofline fraction.
 
-    python bench_extra.py korc_f32 | korc_f64 | loss | cli | fused
+    python bench_extra.py korc_f32 | korc_f64 | loss | cli | fused | deposition
 """
 import json
 import os
@@ -237,6 +237,100 @@ def fused(n=1000000, steps=200, per_launch=10):
     return {"workload": "solver_kernel, %d steps per launch" % per_launch, "value": n*steps/elapsed, "unit": "ray-steps/s"}
 
 
+def _host_bin(columns):
+    """numpy's scatter-add on one chunk of samples: the cells by searchsorted, numpy.add.at on a private grid."""
+    x, y, z, value, edges = columns
+    cells = [e.size - 1 for e in edges]
+    inside = np.ones(x.size, dtype=bool)
+    index = []
+    for e, c in zip(edges, (x, y, z)):
+        inside &= (c >= e[0]) & (c < e[-1])
+        index.append(np.searchsorted(e, c, side="right") - 1)
+    flat = (index[0][inside]*cells[1] + index[1][inside])*cells[2] + index[2][inside]
+    grid = np.zeros(cells[0]*cells[1]*cells[2])
+    np.add.at(grid, flat, value[inside])
+    return grid
+
+
+def deposition(which="both", rays=100000, records=1000, cells=64):
+    """The binning stage (gfhip_bins_add, csrc/deposition.hip) at the benchmark's size: 1e5 rays x 1000 records = 1e8
+    samples on a 64^3 grid.  Two inputs: identical rays (every wave takes the wave-uniform path: three atomics per
+    wave) and the CLI beam (rays spread over the bins of a slab: up to three atomics per sample).  Each is timed
+    record by record (1000 adds of 1e5 samples, the pipeline's shape: 3.2 MB per launch) and as 10 adds of 1e7
+    samples (the kernel's own rate); the floor is the 32 B read per sample.  The only existing alternative is
+    numpy.add.at on the host: timed on 16 processes with private grids (its sums depend on the order)."""
+    import multiprocessing
+    from graph_framework_amd.xrays import cli_distribution
+    box = ((1.4, 2.6), (-0.5, 0.5), (-0.25, 0.25))
+    edges = [np.linspace(low, high, cells + 1) for low, high in box]
+    distinct = 20                                             # records held on the device, walked round and round
+    beam = cli_distribution(rays, seed=0)
+    rng = np.random.default_rng(0)
+    inputs = {"identical": [], "cli_beam": []}
+    for r in range(distinct):
+        inward = 1.0 - 0.4*r/distinct                        # x from 2.5 towards 1.5
+        inputs["identical"].append([np.full(rays, 2.5*inward), np.zeros(rays), np.zeros(rays), np.full(rays, 1.0e-3*inward)])
+        inputs["cli_beam"].append([beam["x"]*inward, beam["y"]*inward, beam["z"].copy(), rng.uniform(0.0, 1.0e-3, rays)])
+    big = 100                                                 # records per large add: 1e7 samples
+    out = {"workload": "deposition: %d rays x %d records on a %d^3 grid" % (rays, records, cells), "unit": "samples/s"}
+
+#  The host alternative first: no process forks once the GPU is open.
+    chunks = [[np.concatenate([inputs["cli_beam"][r % distinct][c] for r in range(10)]) for c in range(4)] + [edges]
+              for _ in range(16)]
+    with multiprocessing.get_context("fork").Pool(16) as pool:
+        pool.map(_host_bin, [[c[:1000] for c in chunk[:4]] + [edges] for chunk in chunks])         # workers started
+        start = time.perf_counter()
+        grids = pool.map(_host_bin, chunks)
+        total = np.sum(grids, axis=0)
+        elapsed = time.perf_counter() - start
+    out["numpy_add_at_16_processes"] = {"samples": 16*10*rays, "samples_per_s": 16*10*rays/elapsed, "sum": float(total.sum())}
+
+    from graph_framework_amd import Context, _lib, key_of
+    from graph_framework_amd.deposition import Deposition
+    context = Context(0)
+
+    def buffers(tag, columns):
+        keys = []
+        for name, column in zip("xyzv", columns):
+            key = "%s_%s" % (tag, name)
+            context._check(context.lib.gfhip_allocate_buffer(context.handle, key_of(key), column.size, _lib.GFIR_F64))
+            context.copy_to_device(key, column)
+            keys.append(key)
+        return keys
+
+    for name in (("identical", "cli_beam") if which == "both" else (which,)):
+        small = [buffers("%s%d" % (name, r), inputs[name][r]) for r in range(distinct)]
+        large = buffers(name + "_large", [np.concatenate([inputs[name][r % distinct][c] for r in range(big)]) for c in range(4)])
+        grid = Deposition(context, *edges)
+        grid.add(*small[0], rays)
+        grid.add(*large, big*rays)                            # warm-up, counted below
+        context.wait()
+        start = time.perf_counter()
+        for r in range(records):
+            grid.add(*small[r % distinct], rays)
+        context.wait()
+        by_record = time.perf_counter() - start
+        repeats = records//big
+        start = time.perf_counter()
+        for _ in range(repeats):
+            grid.add(*large, big*rays)
+        context.wait()
+        at_once = time.perf_counter() - start
+        counts = grid.counts()
+        bins = grid.read(1.0)
+        grid.close()
+        assert counts["samples"] == (1 + big + records + repeats*big)*rays and counts["skipped"] == 0
+        rate = repeats*big*rays/at_once
+        out[name] = {"record_by_record_samples_per_s": records*rays/by_record, "us_per_record": 1.0e6*by_record/records,
+                     "samples_per_s": rate, "ms_per_1e7_samples": 1.0e3*at_once/repeats,
+                     "outside": counts["outside"], "occupied_bins": int(np.count_nonzero(bins)),
+                     "roofline": {"bound": "hbm", "achieved": rate*32/1.0e9, "peak": 8000.0, "unit": "GB/s",
+                                  "frac": rate*32/8.0e12, "note": "32 B read per sample"}}
+    context.close()
+    out["value"] = out.get("cli_beam", out.get("identical"))["samples_per_s"]
+    return out
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "korc_f32"
     if what.startswith("korc"):
@@ -257,6 +351,8 @@ if __name__ == "__main__":
         out = fused()
     elif what == "absorption":
         out = absorption()
+    elif what.startswith("deposition"):
+        out = deposition(what[len("deposition_"):] or "both")
     else:
         raise SystemExit("unknown workload")
     print(json.dumps(out))

@@ -5,13 +5,16 @@ with a record every `sub_steps`, result<rank>.nc) on the MI355X backend.
 
     python examples/trace_rays.py --rays 100000 --steps 1000 --sub-steps 100 [--output /tmp/rays]
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping
+    python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4
     python examples/trace_rays.py --equilibrium vmec --rays 20000 --steps 10 --sub-steps 2 --output /tmp/vmec_rays
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/trace_rays.py ...
 
 One process per GPU; the ensemble is split as the reference splits it over device threads; every rank
 writes its own file (as the reference does).  The exported work items fix dt = 1e-3.
 With --absorption-model the two stages that follow the trace in graph_driver/xrays.cpp:1100-1105 run on
-the same file: calculate_power (kamp per stored record) and bin_power (power, d_power).
+the same file: calculate_power (kamp per stored record) and bin_power (power, d_power).  With --bins and
+--bin-box as well, bin_power also bins d_power on that grid as it goes (utilities/bin.py's profile, exact sums)
+and the rank writes <output>_bins<rank>.nc: its own rays' sums divided by its own ray count.
 """
 import argparse
 import os
@@ -49,7 +52,12 @@ def main():
                              "is a 54 k-record item that runs as 10 segment kernels")
     parser.add_argument("--absorption-model", choices=["weak_damping", "root_find"], default=None,
                         help="after the trace: kamp and power into the result file (needs --output)")
+    parser.add_argument("--bins", default=None, metavar="NX,NY,NZ",
+                        help="with --absorption-model and --bin-box: the deposition profile of utilities/bin.py on this grid")
+    parser.add_argument("--bin-box", default=None, metavar="X0,X1,Y0,Y1,Z0,Z1", help="the box the grid divides")
     args = parser.parse_args()
+    if (args.bins is None) != (args.bin_box is None):
+        parser.error("--bins and --bin-box go together")
 
     import torch
     from graph_framework_amd import distributed
@@ -94,7 +102,26 @@ def main():
         records = args.steps//args.sub_steps
         start = time.perf_counter()
         run_absorption(path, records, index=local_rank, model=args.absorption_model)
-        bin_power(path, records, index=local_rank)
+        context = deposition = None
+        if args.bins:
+            from graph_framework_amd import Context
+            from graph_framework_amd.deposition import Deposition
+            cells = [int(v) for v in args.bins.split(",")]
+            box = [float(v) for v in args.bin_box.split(",")]
+            edges = [np.linspace(box[2*a], box[2*a + 1], cells[a] + 1) for a in range(3)]
+            context = Context(local_rank)
+            deposition = Deposition(context, *edges)
+        bin_power(path, records, index=local_rank, deposition=deposition)
+        if deposition:
+            from graph_framework_amd.output import write_bins
+            counts = deposition.counts()
+            bins = deposition.read(end - begin)
+            deposition.close()
+            context.close()
+            write_bins("%s_bins%d.nc" % (args.output, rank), bins, *edges, **counts)
+            print("rank %d: deposition on %s cells: %d samples, %d outside, %d skipped; sum of bins %.6e"
+                  % (rank, "x".join(str(c) for c in cells), counts["samples"], counts["outside"], counts["skipped"],
+                     float(bins.sum())))
         elapsed = time.perf_counter() - start
         result = ResultFile(path)
         power = result.read("power", records)

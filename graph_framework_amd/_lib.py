@@ -70,6 +70,14 @@ SYMBOLS = [
     ("gfhip_enable_timing", _I, [_P, _I]),
     ("gfhip_kernel_timing", _I, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_U64)]),
     ("gfhip_kernel_timing_samples", _I, [_P, ctypes.POINTER(ctypes.c_double), _S, ctypes.POINTER(_S)]),
+    ("gfhip_bins_create", _P, [_P, _P, _S, _P, _S, _P, _S]),
+    ("gfhip_bins_add", _I, [_P, _U64, _U64, _U64, _U64, _S]),
+    ("gfhip_bins_counts", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("gfhip_bins_state", _I, [_P, _P]),
+    ("gfhip_bins_merge", _I, [_P, _P, _U64, _U64, _U64]),
+    ("gfhip_bins_read", _I, [_P, ctypes.c_double, _P]),
+    ("gfhip_bins_destroy", None, [_P]),
+    ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 
 _lib = None

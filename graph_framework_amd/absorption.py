@@ -125,8 +125,13 @@ def run_absorption(filename, num_steps, index=0, model="weak_damping"):
     return power
 
 
-def bin_power(filename, num_steps, index=0, stream=None, item=None):
-    """bin_power's per-shard body (xrays.cpp:694-786)."""
+def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=None):
+    """bin_power's per-shard body (xrays.cpp:694-786).
+
+    deposition: a deposition.Deposition (on any context).  Every record's x, y, z and d_power are then binned on
+    its grid from the device buffers, right behind the `power` item on the same stream — what
+    deposition.bin_deposition would find in the file afterwards, record 0 (d_power = 0) included, without a second
+    pass over it — and the exact state is merged into `deposition` at the end."""
     file = ResultFile(filename)
     n = file.num_rays
     work = Manager(index, stream)
@@ -142,6 +147,13 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None):
     for name in ("x", "y", "z"):                                            # dataset.read(file, 0) ... :767-771
         host[name][:] = file.read(name, 0)
         host[name + "_last"][:] = host[name]
+    local = None
+    if deposition is not None:
+        from .deposition import Deposition
+        local = Deposition(work.context, *deposition.edges)
+        for name in ("x", "y", "z"):
+            work.copy_to_device(name, host[name])
+        local.add("x", "y", "z", "d_power", n)
     work.wait()                                                             # mirrors hold the initial values
     file.write({"power": power.copy(), "d_power": d_power.copy()}, index=0)
     sync = _Writer()
@@ -154,11 +166,16 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None):
         host["kamp"][:] = file.read("kamp", j, part=1)                      # reference_imag_variable
         work.copy_to_device("kamp", host["kamp"])
         work.run()
+        if local is not None:
+            local.add("x", "y", "z", "d_power", n)
         sync.join()
         work.wait()
         record = {"power": power.copy(), "d_power": d_power.copy()}
         sync.start(lambda record=record, j=j: file.write(record, index=j))
     sync.join()
     file.close()
+    if local is not None:
+        deposition.merge(local.state(), **local.counts())
+        local.close()
     work.context.close()
     return item

@@ -34,6 +34,7 @@
 #include "segments.hpp"
 
 #include "converge_state.hpp"
+#include "superacc.hpp"
 
 namespace gfhip {
 void launch_max_reduce(const void *in, const size_t n, const bool f64,
@@ -41,6 +42,13 @@ void launch_max_reduce(const void *in, const size_t n, const bool f64,
 void launch_converge_decide(const bool f64, unsigned long long *reduced, void *state, hipStream_t stream);
 void launch_converge_decide_batch(const bool f64, unsigned long long *reduced, void *state, const unsigned int count, hipStream_t stream);
 void launch_max_modulus(const void *in, const size_t n, const bool f64, void *result, hipStream_t stream);
+//  deposition.hip
+void launch_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
+                    const double *edges, const int nx, const int ny, const int nz, const double *scale,
+                    void *state, unsigned long long *counters, const unsigned int num_cus, hipStream_t stream);
+void launch_bins_normalise(void *state, const size_t cells, hipStream_t stream);
+void launch_bins_round(const void *state, const size_t cells, const double divisor, double *bins, hipStream_t stream);
+void launch_bins_merge(void *state, const void *other, const size_t words, hipStream_t stream);
 }
 
 namespace {
@@ -133,6 +141,7 @@ struct gfhip_context {
     std::map<uint64_t, buffer> buffers;
     std::map<uint64_t, device_ptr<>> random_states;    // MT19937 states per random_state node (raw bytes)
     std::vector<std::unique_ptr<gfhip_kernel>> kernels;
+    std::vector<std::unique_ptr<gfhip_bins>> bins;     // deposition grids (gfhip_bins_create), until gfhip_bins_destroy
     std::string error;
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
@@ -190,6 +199,19 @@ struct gfhip_kernel {
     std::vector<event_pair> free_events;
     uint64_t launch_count = 0;
     std::vector<double> samples;                   // durations drained by the last gfhip_kernel_timing
+};
+
+//  A 3-D deposition grid: per cell the 67 limbs of superacc.hpp, [cell][limb].
+struct gfhip_bins {
+    gfhip_context *ctx = nullptr;
+    int n[3] = {0, 0, 0};
+    size_t cells = 0;
+    double scale[3] = {0.0, 0.0, 0.0};                 // n/(last edge - first edge): the kernel's first guess of a cell
+    device_ptr<double> edges;                          // the three axes' edges one after the other
+    device_ptr<> state;
+    device_ptr<unsigned long long> counters;           // samples, outside, skipped
+    device_ptr<double> rounded;                        // what gfhip_bins_read copies out (allocated by the first read)
+    uint64_t pending = 0;                              // deposits since the state was last canonical
 };
 
 #define GFHIP_TRY(ctx, call, what) do { if ((ctx)->check((call), (what))) return 1; } while (0)
@@ -1491,5 +1513,183 @@ extern "C" int gfhip_kernel_timing_samples(gfhip_kernel *k, double *ms, size_t c
     const size_t n = k->samples.size() < capacity ? k->samples.size() : capacity;
     if (ms && n) std::memcpy(ms, k->samples.data(), n*sizeof(double));
     if (count) *count = k->samples.size();
+    return 0;
+}
+
+//  Deposition grids (deposition.hip, superacc.hpp).  The limits of a grid: at most 2047 cells per axis, so that the
+//  three axes' edges (3 x 2048 doubles, 48 KiB) fit the LDS a workgroup gets without asking; at most 2^25 cells
+//  (536 B each: 16.8 GiB of state), so that cell*64 + limb fits the 32-bit key the deposit kernel compares.
+static const size_t bins_axis_limit = 2047, bins_cell_limit = static_cast<size_t> (1) << 25;
+
+extern "C" gfhip_bins *gfhip_bins_create(gfhip_context *ctx, const double *xedges, size_t nx,
+                                         const double *yedges, size_t ny, const double *zedges, size_t nz) {
+    if (!ctx) return nullptr;
+    const double *axes[3] = {xedges, yedges, zedges};
+    const size_t n[3] = {nx, ny, nz};
+    std::vector<double> edges;
+    size_t cells = 1;
+    for (int a = 0; a < 3; a++) {
+        if (!axes[a] || n[a] < 1 || n[a] > bins_axis_limit) {
+            ctx->fail("a deposition grid has 1 to 2047 cells per axis");
+            return nullptr;
+        }
+        for (size_t i = 0; i <= n[a]; i++) {
+            if (!std::isfinite(axes[a][i]) || (i && !(axes[a][i - 1] < axes[a][i]))) {
+                ctx->fail("the edges of a deposition grid must be finite and strictly increasing");
+                return nullptr;
+            }
+        }
+        edges.insert(edges.end(), axes[a], axes[a] + n[a] + 1);
+        cells *= n[a];
+    }
+    if (cells > bins_cell_limit) {
+        ctx->fail("a deposition grid has at most 2^25 cells (536 B each)");
+        return nullptr;
+    }
+    if (ctx->check(hipSetDevice(ctx->device), "hipSetDevice")) return nullptr;
+    std::unique_ptr<gfhip_bins> b(new gfhip_bins);
+    b->ctx = ctx;
+    b->cells = cells;
+    for (int a = 0; a < 3; a++) {
+        b->n[a] = static_cast<int> (n[a]);
+        b->scale[a] = static_cast<double> (n[a])/(axes[a][n[a]] - axes[a][0]);
+    }
+    const size_t bytes = cells*gfhip::superacc::limbs*sizeof(int64_t);
+    if (ctx->check(allocate(b->edges, edges.size()*sizeof(double)), "hipMalloc(edges)") ||
+        ctx->check(hipMemcpy(b->edges.get(), edges.data(), edges.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
+        ctx->check(allocate(b->state, bytes), "hipMalloc(bins)") ||
+        ctx->check(hipMemset(b->state.get(), 0, bytes), "hipMemset(bins)") ||
+        ctx->check(allocate(b->counters, 3*sizeof(unsigned long long)), "hipMalloc(counters)") ||
+        ctx->check(hipMemset(b->counters.get(), 0, 3*sizeof(unsigned long long)), "hipMemset(counters)")) {
+        return nullptr;
+    }
+    ctx->bins.push_back(std::move(b));
+    return ctx->bins.back().get();
+}
+
+extern "C" void gfhip_bins_destroy(gfhip_bins *b) {
+    if (!b) return;
+    gfhip_context *ctx = b->ctx;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (auto it = ctx->bins.begin(); it != ctx->bins.end(); ++it) {
+        if (it->get() == b) {
+            ctx->bins.erase(it);
+            return;
+        }
+    }
+}
+
+//  The state canonical in place: before the deposits since the last time could reach 2^30 (a limb takes 2^31),
+//  before the state is handed out and before it is rounded.  Later deposits add to the canonical digits.
+static int bins_normalise(gfhip_bins *b) {
+    gfhip::launch_bins_normalise(b->state.get(), b->cells, b->ctx->stream);
+    b->pending = 0;
+    return b->ctx->check(hipGetLastError(), "normalise launch");
+}
+
+extern "C" int gfhip_bins_add(gfhip_bins *b, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count) {
+    if (!b) return 1;
+    gfhip_context *ctx = b->ctx;
+//  Misuse is reported before anything is enqueued.
+    const uint64_t keys[4] = {x_key, y_key, z_key, value_key};
+    const double *columns[4];
+    for (int c = 0; c < 4; c++) {
+        const buffer *found = find_buffer(ctx, keys[c]);
+        if (!found) return 1;
+        if (found->dtype != GFIR_F64) return ctx->fail("deposition reads fp64 buffers");
+        if (found->count < count) return ctx->fail("a deposition buffer is shorter than the sample count");
+        columns[c] = static_cast<const double *> (found->pointer);
+    }
+    if (enter(ctx)) return 1;
+    for (size_t first = 0; first < count;) {
+        const size_t piece = std::min<size_t> (count - first, gfhip::superacc::deposits_per_normalise);
+        if (b->pending + piece > gfhip::superacc::deposits_per_normalise && bins_normalise(b)) return 1;
+        gfhip::launch_deposit(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
+                              b->edges.get(), b->n[0], b->n[1], b->n[2], b->scale, b->state.get(), b->counters.get(),
+                              ctx->num_cus, ctx->stream);
+        GFHIP_TRY(ctx, hipGetLastError(), "deposit launch");
+        b->pending += piece;
+        first += piece;
+    }
+    return 0;
+}
+
+extern "C" int gfhip_bins_counts(gfhip_bins *b, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
+    if (!b) return 1;
+    gfhip_context *ctx = b->ctx;
+    if (enter(ctx)) return 1;
+    unsigned long long host[3] = {0, 0, 0};
+    GFHIP_TRY(ctx, hipMemcpyAsync(host, b->counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (samples) *samples = host[0];
+    if (outside) *outside = host[1];
+    if (skipped) *skipped = host[2];
+    return 0;
+}
+
+extern "C" int gfhip_bins_state(gfhip_bins *b, int64_t *limbs) {
+    if (!b || !limbs) return 1;
+    gfhip_context *ctx = b->ctx;
+    if (enter(ctx) || bins_normalise(b)) return 1;
+    GFHIP_TRY(ctx, hipMemcpyAsync(limbs, b->state.get(), b->cells*gfhip::superacc::limbs*sizeof(int64_t), hipMemcpyDeviceToHost,
+                                  ctx->stream), "hipMemcpyAsync(bins)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+extern "C" int gfhip_bins_merge(gfhip_bins *b, const int64_t *limbs, uint64_t samples, uint64_t outside, uint64_t skipped) {
+    if (!b || !limbs) return 1;
+    gfhip_context *ctx = b->ctx;
+    if (enter(ctx)) return 1;
+    const size_t words = b->cells*gfhip::superacc::limbs;
+    const unsigned long long counts[3] = {samples, outside, skipped};
+    device_ptr<> other;                                // the incoming limbs, then the three counts
+    GFHIP_TRY(ctx, allocate(other, (words + 3)*sizeof(int64_t)), "hipMalloc(merge)");
+    char *counts_at = static_cast<char *> (other.get()) + words*sizeof(int64_t);
+    GFHIP_TRY(ctx, hipMemcpyAsync(other.get(), limbs, words*sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
+    GFHIP_TRY(ctx, hipMemcpyAsync(counts_at, counts, sizeof(counts), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
+//  Canonical digits (below 2^32) on top of a state that 2^30 deposits may have reached: still inside a limb.
+    gfhip::launch_bins_merge(b->state.get(), other.get(), words, ctx->stream);
+    gfhip::launch_bins_merge(b->counters.get(), counts_at, 3, ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "merge launch");
+    if (bins_normalise(b)) return 1;
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // `other` is freed on return
+    return 0;
+}
+
+extern "C" int gfhip_bins_read(gfhip_bins *b, double divisor, double *bins) {
+    if (!b || !bins) return 1;
+    gfhip_context *ctx = b->ctx;
+    if (enter(ctx)) return 1;
+    if (!b->rounded) GFHIP_TRY(ctx, allocate(b->rounded, b->cells*sizeof(double)), "hipMalloc(rounded bins)");
+    if (bins_normalise(b)) return 1;
+    gfhip::launch_bins_round(b->state.get(), b->cells, divisor, b->rounded.get(), ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "round launch");
+    GFHIP_TRY(ctx, hipMemcpyAsync(bins, b->rounded.get(), b->cells*sizeof(double), hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpyAsync(rounded bins)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+//  Host side, no device: the functions of superacc.hpp that the kernels run, on one accumulator.
+extern "C" int gfhip_exact_sum(const double *values, size_t count, double *sum, int64_t *limbs) {
+    if ((!values && count) || !sum) return 1;
+    int64_t acc[gfhip::superacc::limbs] = {0};
+    uint64_t pending = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (!gfhip::superacc::is_finite(values[i])) {
+            creation_error = "gfhip_exact_sum takes finite values";
+            return 1;
+        }
+        if (++pending > gfhip::superacc::deposits_per_normalise) {
+            gfhip::superacc::normalise(acc);
+            pending = 1;
+        }
+        gfhip::superacc::deposit(acc, values[i]);
+    }
+    gfhip::superacc::normalise(acc);
+    *sum = gfhip::superacc::round(acc);
+    if (limbs) std::memcpy(limbs, acc, sizeof(acc));
     return 0;
 }

@@ -305,6 +305,83 @@ class ResultFile:
             self.file = None
 
 
+class BinsFile(ResultFile):
+    """The file utilities/bin.py writes (bin.py:19-30): fixed dimensions, each variable on dimensions of its own, in
+    the same on-disk conventions as ResultFile."""
+
+    def __init__(self, path):
+        self.lib = _hdf5()
+        self.lock = threading.Lock()
+        hid = ctypes.c_int64
+        self.native = hid.in_dll(self.lib, "H5T_NATIVE_DOUBLE_g").value
+        self.native_int = hid.in_dll(self.lib, "H5T_NATIVE_INT_g").value
+        self.native_int64 = hid.in_dll(self.lib, "H5T_NATIVE_INT64_g").value
+        self.string = hid.in_dll(self.lib, "H5T_C_S1_g").value
+        self.scale_type = hid.in_dll(self.lib, "H5T_IEEE_F32BE_g").value
+        self.dataset_create = hid.in_dll(self.lib, "H5P_CLS_DATASET_CREATE_ID_g").value
+        self.file = self.lib.H5Fcreate(path.encode(), _H5F_ACC_TRUNC, 0, 0)
+        if self.file < 0:
+            raise IOError("cannot create %s" % path)
+        self._string_attribute(self.file, "_NCProperties", "version=2,graph_framework_amd=1,hdf5=1.10", None)
+        self.scales = {}                                     # name -> (dataset, dimid)
+
+    def create_dimension(self, name, length):
+        """createDimension(name, length)."""
+        self.scales[name] = (self._dimension(name, int(length), len(self.scales)), len(self.scales))
+
+    def write_variable(self, name, values, dimensions):
+        """createVariable(name, 'f8', dimensions) and its values."""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.shape == tuple(self._extent(self.scales[d][0])[0] for d in dimensions)
+        space = self.lib.H5Screate_simple(values.ndim, (ctypes.c_uint64*values.ndim)(*values.shape), None)
+        dataset = self.lib.H5Dcreate2(self.file, name.encode(), self.native, space, 0, 0, 0)
+        self.lib.H5Sclose(space)
+        if dataset < 0:
+            raise IOError("cannot create variable %s" % name)
+        for index, dimension in enumerate(dimensions):
+            if self.lib.hl.H5DSattach_scale(dataset, self.scales[dimension][0], index) < 0:
+                raise IOError("H5DSattach_scale failed for %s" % name)
+        self._int_attribute(dataset, "_Netcdf4Coordinates", [self.scales[d][1] for d in dimensions])
+        status = self.lib.H5Dwrite(dataset, self.native, 0, 0, 0, values.ctypes.data)
+        self.lib.H5Dclose(dataset)
+        if status < 0:
+            raise IOError("H5Dwrite failed for %s" % name)
+
+    def int64_attribute(self, name, value):
+        """A global attribute of type NC_INT64."""
+        space = self.lib.H5Screate(_H5S_SCALAR)
+        attribute = self.lib.H5Acreate2(self.file, name.encode(), self.native_int64, space, 0, 0)
+        if attribute < 0:
+            raise IOError("cannot create attribute %s" % name)
+        self.lib.H5Awrite(attribute, self.native_int64, ctypes.byref(ctypes.c_int64(int(value))))
+        self.lib.H5Aclose(attribute)
+        self.lib.H5Sclose(space)
+
+    def close(self):
+        if self.file is not None:
+            for dataset, _ in self.scales.values():
+                self.lib.H5Dclose(dataset)
+            self.lib.H5Fclose(self.file)
+            self.file = None
+
+
+def write_bins(path, bins, xbins, ybins, zbins, samples=0, outside=0, skipped=0):
+    """bins.nc of utilities/bin.py: dimensions nx, ny, nz, nxp, nyp, nzp; f8 variables bins(nx, ny, nz), xbins(nxp),
+    ybins(nyp), zbins(nzp); and what became of the samples as global integer attributes."""
+    bins = np.asarray(bins)
+    file = BinsFile(path)
+    for name, length in zip(("nx", "ny", "nz"), bins.shape):
+        file.create_dimension(name, length)
+    for name, length in zip(("nxp", "nyp", "nzp"), bins.shape):
+        file.create_dimension(name, length + 1)
+    file.write_variable("bins", bins, ("nx", "ny", "nz"))
+    for name, edges, dimension in (("xbins", xbins, "nxp"), ("ybins", ybins, "nyp"), ("zbins", zbins, "nzp")):
+        file.write_variable(name, edges, (dimension,))
+    for name, value in (("samples", samples), ("outside", outside), ("skipped", skipped)):
+        file.int64_attribute(name, value)
+    file.close()
+
+
 #  Variables of the reference's ray files, solver.hpp:338-346.
 RAY_VARIABLES = (("time", "t"), ("residual", "residual"), ("w", "w"), ("x", "x"), ("y", "y"), ("z", "z"),
                  ("kx", "kx"), ("ky", "ky"), ("kz", "kz"))

@@ -36,6 +36,7 @@ extern "C" {
 
 typedef struct gfhip_context gfhip_context;
 typedef struct gfhip_kernel gfhip_kernel;
+typedef struct gfhip_bins gfhip_bins;
 
 /* Number of devices = number of host threads/ranks a driver should start.
  * Replaces  static size_t max_concurrency()   (cuda_context.hpp:121-125, jit.hpp:87). */
@@ -250,6 +251,43 @@ int gfhip_kernel_timing(gfhip_kernel *kernel, double *average_ms, uint64_t *laun
  * (which this call performs first if launches are pending): up to `capacity`
  * values into `ms`, the number available into `count`. */
 int gfhip_kernel_timing_samples(gfhip_kernel *kernel, double *ms, size_t capacity, size_t *count);
+
+/* Deposition: per-sample values binned on a 3-D grid, every cell the EXACT sum of its samples, correctly
+ * rounded once when it is read.  This is the device form of utilities/bin.py (which sums d_power over
+ * nx*ny*nz boolean masks): a sample (x, y, z, value) belongs to cell (i, j, k) iff
+ * edge[i] <= c && c < edge[i+1] on each axis (bin.py:54-56), cells are stored bins[nx][ny][nz].  A cell is
+ * an integer superaccumulator (csrc/superacc.hpp: 67 limbs of 64 bits, limb k of weight 2^(32k - 1074)),
+ * fed with 64-bit integer atomics, so the result does not depend on the order of the samples, on how they
+ * are split into records, files or ranks, or on the run.
+ *
+ * gfhip_bins_create: each axis has n + 1 finite, strictly increasing edges.  Limits: 1 <= n <= 2047 per
+ *   axis (the edges are staged in 48 KiB of LDS) and nx*ny*nz <= 2^25 cells (536 B each).  Returns NULL on
+ *   failure (gfhip_last_error(ctx)).  The grid belongs to the context and is freed with it at the latest.
+ * gfhip_bins_add: `count` samples from four fp64 context buffers (gfhip_allocate_buffer,
+ *   gfhip_copy_to_device, or a kernel's outputs), asynchronous on the context's stream.  A sample with a
+ *   coordinate outside [edge[0], edge[n]) or NaN on any axis lands nowhere and counts as `outside`; a
+ *   sample inside the grid whose value is NaN or +-inf is not added and counts as `skipped`
+ *   (utilities/fix_NaN.py:55 drops NaNs the same way).  Buffers that are unknown, not fp64 or shorter than
+ *   `count` are refused before anything is launched.
+ * gfhip_bins_counts: samples seen, and of those the ones outside and skipped; synchronises.
+ * gfhip_bins_state: the canonical limbs, nx*ny*nz*67 (digits in [0, 2^32) in limbs 0-65, the sign in limb
+ *   66): byte-identical for the same multiset of samples whatever their order; synchronises.
+ * gfhip_bins_merge: add another grid's canonical limbs and counts (same edges: the caller's business).
+ * gfhip_bins_read: bins[cell] = round_to_nearest_even(exact sum)/divisor, the division being IEEE: two
+ *   roundings, as bin.py's power_bins/total; synchronises. */
+gfhip_bins *gfhip_bins_create(gfhip_context *ctx, const double *xedges, size_t nx,
+                              const double *yedges, size_t ny, const double *zedges, size_t nz);
+int gfhip_bins_add(gfhip_bins *bins, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count);
+int gfhip_bins_counts(gfhip_bins *bins, uint64_t *samples, uint64_t *outside, uint64_t *skipped);
+int gfhip_bins_state(gfhip_bins *bins, int64_t *limbs);
+int gfhip_bins_merge(gfhip_bins *bins, const int64_t *limbs, uint64_t samples, uint64_t outside, uint64_t skipped);
+int gfhip_bins_read(gfhip_bins *bins, double divisor, double *values);
+void gfhip_bins_destroy(gfhip_bins *bins);
+
+/* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
+ * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
+ * Non-zero for a NaN or an infinity among the values (gfhip_last_error(NULL)). */
+int gfhip_exact_sum(const double *values, size_t count, double *sum, int64_t *limbs);
 
 #ifdef __cplusplus
 }
