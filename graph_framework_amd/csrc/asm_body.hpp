@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "gfir_item.hpp"
+#include "merge.hpp"
 #include "options.hpp"
 #include "schedule.hpp"
 #include "tables.hpp"
@@ -254,7 +255,7 @@ class asm_body_writer {
         std::vector<bool> group_seen(groups.size(), false);
         for (size_t i = 0; i < n; i++) {
             const gfir_instruction &c = it.code[i];
-            if (c.op == GFIR_CONST || c.op == GFIR_INPUT) continue;
+            if (c.op == GFIR_CONST || c.op == GFIR_INPUT || it.is_merged(i)) continue;    // (a merged record reads nothing: merge.hpp)
             if (c.op == GFIR_GATHER1 || c.op == GFIR_GATHER2) {
 //  The arguments are read where the group's cell is found: at its first gather.
                 const size_t g = static_cast<size_t> (node_group[i]);
@@ -792,6 +793,11 @@ class asm_body_writer {
         const gfir_instruction &c = it.code[i];
         position = i;
         pinned.clear();
+        if (it.is_merged(i)) {
+//  A record merged into an earlier one (merge.hpp): no instruction, every use names the representative.
+            line("; alias r" + std::to_string(i) + " = r" + std::to_string(it.merged_into[i]));
+            return;
+        }
         look_ahead();
         std::vector<int64_t> read = used_at[i];
         switch (c.op) {
@@ -1043,6 +1049,8 @@ class asm_body_writer {
 ///  lifted; with two waves per SIMD a lane has 40 slots at most, the RK4 item needs 19 with its best order and 65
 ///  with the order schedule_for_pressure picks for the compiler.
 //------------------------------------------------------------------------------
+///  With options.merge the statement of a candidate is written for its merged form (merge.hpp: the representative of equal
+///  records is the earliest in the candidate's order); the order comes back unmerged.
 ///  `directories`: where the seed of the chosen order is remembered (`<hash of item and knobs>.order`, next to the code
 ///  objects of the kernel cache): the search then runs once per item and machine, not once per process.
 inline item schedule_for_assembly(const item &in, const codegen_options &opt, const std::vector<std::string> &directories = {}) {
@@ -1054,7 +1062,8 @@ inline item schedule_for_assembly(const item &in, const codegen_options &opt, co
     const uint64_t key = fnv1a(std::string(bytes.begin(), bytes.end()) + "|order|" + std::to_string(opt.asm_pool_lo) + "|" +
                                std::to_string(opt.asm_load_ahead) + "|" + std::to_string(opt.asm_reload_ahead) + "|" +
                                std::to_string(opt.asm_schedule_tries) + "|" + std::to_string(opt.asm_wide_loads) + "|" +
-                               std::to_string(opt.lds_budget) + "|" + std::to_string(opt.compact_tables) + "|" + std::to_string(opt.block_size));
+                               std::to_string(opt.lds_budget) + "|" + std::to_string(opt.compact_tables) + "|" + std::to_string(opt.block_size) +
+                               (opt.merge ? "|merged" : ""));
     char name[40];
     std::snprintf(name, sizeof(name), "/%016llx.order", static_cast<unsigned long long> (key));
     for (auto &directory : directories) {
@@ -1074,7 +1083,8 @@ inline item schedule_for_assembly(const item &in, const codegen_options &opt, co
                          : std::max<uint32_t> (4u, static_cast<uint32_t> (opt.asm_schedule_tries*5000ull/in.code.size()));
     for (uint32_t seed = 0; seed < std::max(1u, tries); seed++) {
         item candidate = reorder(in, list_schedule(in, seed));
-        asm_body_writer writer(candidate, opt, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column,
+        const item merged = opt.merge ? merge_records(candidate) : item();
+        asm_body_writer writer(opt.merge ? merged : candidate, opt, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column,
                                opt.block_size, 1u << 20);
         const asm_body_text text = writer.write();
         if (!text.ok) continue;

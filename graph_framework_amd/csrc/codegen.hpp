@@ -36,7 +36,8 @@
 ///  segments.hpp (items cut into several kernels, the redo launch), asm_body.hpp
 ///  (the pass of a large fp64 item as gfx950 assembly with a register assignment
 ///  of its own: the RK4 step's default), and lower() below, which writes the
-///  kernel text.
+///  kernel text.  merge.hpp merges the records of an item that hold the same
+///  bits, in emission order, before the item is cut or written.
 //------------------------------------------------------------------------------
 #ifndef gfhip_codegen_hpp
 #define gfhip_codegen_hpp
@@ -241,6 +242,11 @@ struct kernel_writer {
         for (size_t i = 0; i < it.code.size(); i++) {
             const gfir_instruction &c = it.code[i];
             reload(i);
+            if (it.is_merged(i)) {
+//  A record merged into an earlier one (merge.hpp): a second name, so that every record is still defined once.
+                s << ind << "const real r" << i << " = " << N(it.merged_into[i]) << ";\n";
+                continue;
+            }
             {
                 const uint32_t operands[3] = {c.a, c.b, c.c};
                 for (int k = 0; k < operand_count(c.op); k++) define(operands[k]);
@@ -865,6 +871,13 @@ inline lowered lower(const item &original, const codegen_options &opt = codegen_
 //  records of the piece that gfhip_export_piece hands out, tests/asm_symbolic.py)
     if (opt.schedule_for_pressure && !(opt.asm_body && piece.scheduled)) {
         scheduled = schedule_for_pressure(original);
+    }
+//  A whole item (and the redo kernel's copy of it) is merged here, in its emission order (merge.hpp); the segments of
+//  a cut item arrive merged: gf_hip.cpp merges before it cuts.
+    if (opt.merge && (piece.role == piece_role::none || piece.role == piece_role::redo) && original.merged_into.empty()) {
+        merge_report merges;
+        scheduled = merge_records(scheduled.code.empty() ? original : scheduled, &merges);
+        if (std::getenv("GFHIP_ASM_REPORT")) merges.print(stderr, original.name);
     }
     const item &it = scheduled.code.empty() ? original : scheduled;
     lowered out;

@@ -31,6 +31,7 @@
 
 #include "../../include/gf_hip.h"
 #include "codegen.hpp"
+#include "merge.hpp"
 #include "segments.hpp"
 
 #include "converge_state.hpp"
@@ -327,7 +328,7 @@ static uint32_t plan_item(const gfhip::item &it, gfhip::lowered &whole, std::vec
         if (const char *env = std::getenv("GFHIP_CACHE_DIR")) directories.push_back(env);
         directories.push_back(library_directory() + "/kernel_cache");
         ordered = gfhip::schedule_for_assembly(it, opt, directories);
-        as_assembly = gfhip::assembly_fits(ordered, opt);
+        as_assembly = gfhip::assembly_fits(opt.merge ? gfhip::merge_records(ordered) : ordered, opt);
     }
     if (count < 2 && opt.segments != 1 && !as_assembly) {
         whole = gfhip::lower(it, opt);
@@ -335,6 +336,13 @@ static uint32_t plan_item(const gfhip::item &it, gfhip::lowered &whole, std::vec
     }
 //  Cut in the pressure-aware emission order where that is affordable (schedule.hpp), else in the order given.
     if (!as_assembly) ordered = opt.schedule_for_pressure ? gfhip::schedule_for_pressure(it) : it;
+//  Records that hold the same bits become one (merge.hpp), in emission order — the earliest is the one that is computed —
+//  and before the cut: hand-over slots carry representatives only.
+    if (opt.merge) {
+        gfhip::merge_report merges;
+        ordered = gfhip::merge_records(ordered, &merges);
+        if (std::getenv("GFHIP_ASM_REPORT")) merges.print(stderr, it.name);
+    }
     gfhip::segmentation plan = gfhip::split_item(ordered, gfhip::choose_cuts(ordered, count));
 //  A one-kernel item keeps its name (profiles show gfhip_<name> and gfhip_<name>_redo).
     if (plan.segments.size() == 1) plan.segments[0].piece.name = it.name;
@@ -373,7 +381,7 @@ static uint32_t plan_item(const gfhip::item &it, gfhip::lowered &whole, std::vec
         plain.division = gfhip::division_mode::ieee;
         plain.waves_per_simd = 0;
         built_piece &r = redo->emplace();
-        r.plan.piece = it;
+        r.plan.piece = it;                          // (lower() orders and merges it itself)
         r.plan.piece.name = it.name + "_redo";
         r.low = gfhip::lower(r.plan.piece, plain, role);
     }

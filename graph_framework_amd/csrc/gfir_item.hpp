@@ -29,6 +29,10 @@ struct item {
     std::vector<gfir_instruction> code;
     std::vector<uint32_t> outputs;
     std::vector<gfir_setter> setters;
+    std::vector<uint32_t> merged_into;      ///< merge.hpp: per record, the earlier record it is a dead copy of (GFIR_NONE: none);
+                                            ///< empty when nothing is merged.  Not part of the serialized item.
+
+    bool is_merged(const size_t record) const { return !merged_into.empty() && merged_into[record] != GFIR_NONE; }
 
     static size_t element_size(const uint32_t dtype) {
         return dtype == GFIR_F32 ? 4 : dtype == GFIR_C64 ? 16 : 8;

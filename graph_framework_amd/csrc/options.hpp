@@ -65,6 +65,8 @@ struct codegen_options {
     uint32_t asm_load_ahead = 96;       ///< table loads are issued this many nodes ahead of their first use (GFHIP_ASM_LOAD_AHEAD) ...
     uint32_t asm_reload_ahead = 24;     ///< ... LDS reads (values sent out of the registers, LDS-staged tables) this many (GFHIP_ASM_RELOAD_AHEAD).
                                         ///< Measured (profiles/r03_asm_sweep.jsonl): 0/0 2.19 ms, 24/6 1.88, 48/12 1.85, 96/24 1.82; pool from v48: 1.83
+    bool merge = true;                  ///< records that hold the same bits are merged before anything else sees the item (merge.hpp;
+                                        ///< GFHIP_MERGE=0: the item as it arrives)
     size_t handover_bytes = 128u << 20; ///< the hand-over buffers of a segmented item hold one chunk of rays and at most this many
                                         ///< bytes, so that they stay in the 256 MB Infinity Cache (GFHIP_HANDOVER_BYTES)
 
@@ -105,6 +107,7 @@ struct codegen_options {
         if (const char *e = std::getenv("GFHIP_SEGMENT_NODES")) o.segment_nodes = static_cast<uint32_t> (std::atol(e));
         if (const char *e = std::getenv("GFHIP_SEGMENTS")) o.segments = static_cast<uint32_t> (std::atol(e));
         if (const char *e = std::getenv("GFHIP_SEGMENTS_MIN_NODES")) o.segments_min_nodes = static_cast<uint32_t> (std::atol(e));
+        if (const char *e = std::getenv("GFHIP_MERGE")) o.merge = std::string(e) != "0";
         if (const char *e = std::getenv("GFHIP_HANDOVER_BYTES")) o.handover_bytes = static_cast<size_t> (std::atoll(e));
         return o;
     }

@@ -51,6 +51,9 @@ inline item reorder(const item &in, const std::vector<uint32_t> &order) {
     }
     for (auto &s : out.setters) s.value = new_index[s.value];
     for (auto &o : out.outputs) o = new_index[o];
+    for (size_t p = 0; p < order.size() && !in.merged_into.empty(); p++) {
+        out.merged_into[p] = in.is_merged(order[p]) ? new_index[in.merged_into[order[p]]] : GFIR_NONE;
+    }
     return out;
 }
 
@@ -64,8 +67,15 @@ inline item schedule_for_pressure(const item &in) {
     std::vector<bool> is_root(n, false);
     for (auto &s : in.setters) is_root[s.value] = true;
     for (auto o : in.outputs) is_root[o] = true;
+//  A merged record (merge.hpp) is a name for its representative: it reads nothing and follows it at once.
+    std::vector<std::vector<uint32_t>> names(in.merged_into.empty() ? 0 : n);
     for (size_t i = 0; i < n; i++) {
         const gfir_instruction &c = in.code[i];
+        if (in.is_merged(i)) {
+            names[in.merged_into[i]].push_back(static_cast<uint32_t> (i));
+            pending[i] = 1;
+            continue;
+        }
         const uint32_t operands[3] = {c.a, c.b, c.c};
         std::set<uint32_t> distinct;
         for (int k = 0; k < operand_count(c.op); k++) distinct.insert(operands[k]);
@@ -82,7 +92,7 @@ inline item schedule_for_pressure(const item &in) {
     for (size_t i = 0; i < n; i++) {
         const gfir_instruction &c = in.code[i];
         const uint32_t operands[3] = {c.a, c.b, c.c};
-        for (int k = 0; k < operand_count(c.op); k++) {
+        for (int k = 0; k < operand_count(c.op) && !in.is_merged(i); k++) {
             bool seen = false;
             for (int j = 0; j < distinct_count[i]; j++) seen = seen || distinct_operands[3*i + j] == operands[k];
             if (!seen) distinct_operands[3*i + distinct_count[i]++] = operands[k];
@@ -115,6 +125,7 @@ inline item schedule_for_pressure(const item &in) {
         }
         ready.erase(best);
         order.push_back(best);
+        if (!names.empty()) order.insert(order.end(), names[best].begin(), names[best].end());
         for (int k = 0; k < distinct_count[best]; k++) consumers_left[distinct_operands[3*static_cast<size_t> (best) + k]]--;
         for (auto u : users[best]) {
             if (--pending[u] == 0) {
@@ -146,8 +157,14 @@ inline std::vector<uint32_t> list_schedule(const item &in, const uint32_t seed) 
     for (auto o : in.outputs) is_root[o] = true;
     std::vector<uint32_t> distinct_operands(3*n, GFIR_NONE);
     std::vector<uint8_t> distinct_count(n, 0);
+    std::vector<std::vector<uint32_t>> names(in.merged_into.empty() ? 0 : n);   // merged records follow their representative
     for (size_t i = 0; i < n; i++) {
         const gfir_instruction &c = in.code[i];
+        if (in.is_merged(i)) {
+            names[in.merged_into[i]].push_back(static_cast<uint32_t> (i));
+            pending[i] = 1;
+            continue;
+        }
         const uint32_t operands[3] = {c.a, c.b, c.c};
         for (int k = 0; k < operand_count(c.op); k++) {
             bool seen = false;
@@ -187,6 +204,7 @@ inline std::vector<uint32_t> list_schedule(const item &in, const uint32_t seed) 
         const uint32_t pick = best[static_cast<size_t> (next()%best.size())];
         ready.erase(pick);
         order.push_back(pick);
+        if (!names.empty()) order.insert(order.end(), names[pick].begin(), names[pick].end());
         for (int k = 0; k < distinct_count[pick]; k++) consumers_left[distinct_operands[3*static_cast<size_t> (pick) + k]]--;
         for (auto u : users[pick]) {
             if (--pending[u] == 0) {

@@ -28,9 +28,11 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gfir_item.hpp"
@@ -81,7 +83,7 @@ inline std::vector<size_t> choose_cuts(const item &it, const size_t count, const
     for (size_t i = 0; i < n; i++) {
         const gfir_instruction &c = it.code[i];
         const uint32_t operands[3] = {c.a, c.b, c.c};
-        for (int k = 0; k < operand_count(c.op); k++) last_use[operands[k]] = i;
+        for (int k = 0; k < operand_count(c.op) && !it.is_merged(i); k++) last_use[operands[k]] = i;    // (a merged record reads nothing)
     }
     for (auto &s : it.setters) last_use[s.value] = n;
     for (auto o : it.outputs) last_use[o] = n;
@@ -142,10 +144,15 @@ inline segmentation split_item(const item &it, const std::vector<size_t> &cuts) 
             last_segment[value] = std::max(last_segment[value], by);
         }
     };
+//  A merged record (merge.hpp) in the segment of its representative is a name for it there and reads nothing: hand-over
+//  slots carry representatives only.  Cut off from its representative it becomes a constant nobody reads.
+    auto name_of_representative = [&] (const size_t i) {
+        return it.is_merged(i) && segment_of(it.merged_into[i]) == segment_of(i);
+    };
     for (size_t i = 0; i < n; i++) {
         const gfir_instruction &c = it.code[i];
         const uint32_t operands[3] = {c.a, c.b, c.c};
-        for (int k = 0; k < operand_count(c.op); k++) use(operands[k], segment_of(i));
+        for (int k = 0; k < operand_count(c.op) && !it.is_merged(i); k++) use(operands[k], segment_of(i));
     }
     for (auto &s : it.setters) use(s.value, count - 1);
     for (auto o : it.outputs) use(o, count - 1);
@@ -231,9 +238,14 @@ inline segmentation split_item(const item &it, const std::vector<size_t> &cuts) 
             local[value] = static_cast<uint32_t> (piece.code.size() - 1);
             return local[value];
         };
+        std::vector<std::pair<uint32_t, uint32_t>> names;      // (merged record, its representative) of the piece
         for (size_t i = bounds[k]; i < bounds[k + 1]; i++) {
             gfir_instruction c = it.code[i];
-            if (c.op == GFIR_INPUT) {
+            if (it.is_merged(i) && !name_of_representative(i)) {
+                c = gfir_instruction();
+                c.op = GFIR_CONST;
+                c.a = c.b = c.c = GFIR_NONE;
+            } else if (c.op == GFIR_INPUT) {
                 c.a = symbol_for_state(c.a);
             } else {
                 const int operands = operand_count(c.op);
@@ -251,6 +263,7 @@ inline segmentation split_item(const item &it, const std::vector<size_t> &cuts) 
             }
             piece.code.push_back(c);
             local[static_cast<uint32_t> (i)] = static_cast<uint32_t> (piece.code.size() - 1);
+            if (name_of_representative(i)) names.push_back({local[static_cast<uint32_t> (i)], local[it.merged_into[i]]});
         }
 //  Outputs: what later segments read ...
         for (size_t i = bounds[k]; i < bounds[k + 1]; i++) {
@@ -273,6 +286,10 @@ inline segmentation split_item(const item &it, const std::vector<size_t> &cuts) 
                 seg.output_slot.push_back(-1);
                 seg.output_original.push_back(static_cast<int> (o));
             }
+        }
+        if (!names.empty()) {
+            piece.merged_into.assign(piece.code.size(), GFIR_NONE);
+            for (auto &name : names) piece.merged_into[name.first] = name.second;
         }
         result.segments.push_back(std::move(seg));
     }
