@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <set>
@@ -1054,7 +1055,7 @@ class asm_body_writer {
 ///  `directories`: where the seed of the chosen order is remembered (`<hash of item and knobs>.order`, next to the code
 ///  objects of the kernel cache): the search then runs once per item and machine, not once per process.
 inline item schedule_for_assembly(const item &in, const codegen_options &opt, const std::vector<std::string> &directories = {}) {
-    if (in.code.size() > 20000 || !asm_body_writer::why_not(in, opt).empty()) return schedule_for_pressure(in);
+    if (too_large_to_schedule(in) || !asm_body_writer::why_not(in, opt).empty()) return schedule_for_pressure(in);
     if (const char *forced = std::getenv("GFHIP_ASM_SEED")) {         // experiment (profiles/diag/asm/seeds.sh): this tie-break, no search
         return reorder(in, list_schedule(in, static_cast<uint32_t> (std::atoi(forced))));
     }
@@ -1111,14 +1112,31 @@ inline item schedule_for_assembly(const item &in, const codegen_options &opt, co
     return best;
 }
 
-///  Whether the statement of `ordered` can be written within the LDS a workgroup has (lower() decides the same way).
-inline bool assembly_fits(const item &ordered, const codegen_options &opt) {
-    const table_layout layout = layout_tables(ordered, opt);
+///  THE predicate: whether the pass of `piece` is offered to the assembly writer at all (which may still find that
+///  its values do not fit).  plan.hpp asks it for the only piece of an item and for the last piece of a cut one.
+inline bool assembly_candidate(const item &piece, const codegen_options &opt) {
+    return opt.asm_body && !piece.code.empty() && piece.code.size() >= opt.asm_min_nodes && asm_body_writer::why_not(piece, opt).empty();
+}
+
+///  LDS slots the statement may use next to the `lds_used` bytes of staged packs: a workgroup of 256 lanes is one wave
+///  per SIMD of its CU, so `asm_waves` workgroups share the CU's 160 KB.
+inline uint32_t assembly_slot_limit(const size_t lds_used, const codegen_options &opt, const size_t element_size) {
     const size_t per_block = 160u*1024u/opt.asm_waves;
-    const uint32_t slot_limit = layout.lds_used < per_block
-                              ? static_cast<uint32_t> ((per_block - layout.lds_used)/(static_cast<size_t> (opt.block_size)*ordered.element_size())) : 0;
-    asm_body_writer writer(ordered, opt, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column, opt.block_size, slot_limit);
-    return writer.write().ok;
+    return lds_used < per_block ? static_cast<uint32_t> ((per_block - lds_used)/(static_cast<size_t> (opt.block_size)*element_size)) : 0;
+}
+
+///  The statement of `piece` (in emission order, merged) within the LDS a workgroup has; `ok` is false if it cannot be written.
+inline asm_body_text assembly_statement(const item &piece, const codegen_options &opt) {
+    const table_layout layout = layout_tables(piece, opt);
+    asm_body_writer writer(piece, opt, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column, opt.block_size,
+                           assembly_slot_limit(layout.lds_used, opt, piece.element_size()));
+    const asm_body_text text = writer.write();
+    if (std::getenv("GFHIP_ASM_REPORT")) {
+        std::fprintf(stderr, "assembly body of %s: %s; %zu vector, %zu scalar, %zu table loads, %zu LDS reads, %zu LDS writes, %zu waits, %u slots\n",
+                     piece.name.c_str(), text.ok ? "ok" : text.why.c_str(), text.vector, text.scalar, text.loads,
+                     text.lds_reads, text.lds_writes, text.waits, text.slots);
+    }
+    return text;
 }
 
 }  // namespace gfhip

@@ -30,14 +30,16 @@
 ///    runs a second kernel over the output — and `<name>_converge` runs the stall
 ///    loop of workflow.hpp:179-205 per ray inside the launch.
 ///
+///  This file is the writer: in_emission_order() orders and merges a whole item,
+///  write_item() writes the kernel text of an item in the order in which it
+///  arrives.  What is written, and in how many pieces, is decided in plan.hpp.
 ///  Pieces: options.hpp (knobs, cache hash), schedule.hpp (emission order),
-///  tables.hpp (compaction, packs, LDS staging), parking.hpp (values that wait
-///  in LDS), prelude.hpp (device helpers: division, window checks, pow),
-///  segments.hpp (items cut into several kernels, the redo launch), asm_body.hpp
-///  (the pass of a large fp64 item as gfx950 assembly with a register assignment
-///  of its own: the RK4 step's default), and lower() below, which writes the
-///  kernel text.  merge.hpp merges the records of an item that hold the same
-///  bits, in emission order, before the item is cut or written.
+///  merge.hpp (records that hold the same bits become one), tables.hpp
+///  (compaction, packs, LDS staging), parking.hpp (values that wait in LDS),
+///  prelude.hpp (device helpers: division, window checks, pow), segments.hpp
+///  (items cut into several kernels, the redo launch), asm_body.hpp (the pass of
+///  a large fp64 item as gfx950 assembly with a register assignment of its own:
+///  the RK4 step's default).
 //------------------------------------------------------------------------------
 #ifndef gfhip_codegen_hpp
 #define gfhip_codegen_hpp
@@ -57,6 +59,7 @@
 
 #include "asm_body.hpp"
 #include "gfir_item.hpp"
+#include "merge.hpp"
 #include "options.hpp"
 #include "parking.hpp"
 #include "prelude.hpp"
@@ -96,7 +99,6 @@ enum class piece_role { none, middle, last, redo };
 
 struct piece_info {
     piece_role role = piece_role::none;
-    bool scheduled = false;                     ///< the piece arrives in emission order (gf_hip.cpp cut it from the scheduled item)
     std::vector<bool> output_handed_over;       ///< per output: a hand-over value (no stored-value checks apply to it)
     std::vector<bool> symbol_after_division;    ///< per symbol: a handed-over value that depends on a quotient of an earlier segment
                                                 ///< (a zero of it stored here may carry the wrong sign, like a zero computed here)
@@ -247,10 +249,7 @@ struct kernel_writer {
                 s << ind << "const real r" << i << " = " << N(it.merged_into[i]) << ";\n";
                 continue;
             }
-            {
-                const uint32_t operands[3] = {c.a, c.b, c.c};
-                for (int k = 0; k < operand_count(c.op); k++) define(operands[k]);
-            }
+            for (const uint32_t o : it.operands(i)) define(o);
             switch (c.op) {
                 case GFIR_CONST:
                     s << ind << "const real r" << i << " = " << value_literal(c.imm[0], c.imm[1]) << ";\n";
@@ -862,24 +861,43 @@ struct kernel_writer {
 };
 
 //------------------------------------------------------------------------------
-///  @brief Lower one item.
+///  @brief A whole item in emission order, its equal records merged in that order (merge.hpp: the earliest is the one that
+///  is computed).  Every item passes through here once, before it is cut or written; so does the redo kernel's copy.
+///
+///  @param[in] preordered The order the assembly search chose (asm_body.hpp), or nullptr: the order for the compiler
+///                        (schedule.hpp), or the item's own with GFHIP_SCHEDULE=source.
 //------------------------------------------------------------------------------
-inline lowered lower(const item &original, const codegen_options &opt = codegen_options::from_environment(),
-                     const piece_info &piece = piece_info()) {
-    item scheduled;
-//  (the assembly body keeps the order of a piece that is already in emission order: its annotations number the
-//  records of the piece that gfhip_export_piece hands out, tests/asm_symbolic.py)
-    if (opt.schedule_for_pressure && !(opt.asm_body && piece.scheduled)) {
-        scheduled = schedule_for_pressure(original);
-    }
-//  A whole item (and the redo kernel's copy of it) is merged here, in its emission order (merge.hpp); the segments of
-//  a cut item arrive merged: gf_hip.cpp merges before it cuts.
-    if (opt.merge && (piece.role == piece_role::none || piece.role == piece_role::redo) && original.merged_into.empty()) {
+inline item in_emission_order(const item &it, const codegen_options &opt, const item *preordered = nullptr) {
+    item ordered = preordered ? *preordered : opt.schedule_for_pressure ? schedule_for_pressure(it) : it;
+    if (opt.merge) {
         merge_report merges;
-        scheduled = merge_records(scheduled.code.empty() ? original : scheduled, &merges);
-        if (std::getenv("GFHIP_ASM_REPORT")) merges.print(stderr, original.name);
+        ordered = merge_records(ordered, &merges);
+        if (std::getenv("GFHIP_ASM_REPORT")) merges.print(stderr, it.name);
     }
-    const item &it = scheduled.code.empty() ? original : scheduled;
+    return ordered;
+}
+
+///  Per record: whether it depends on the result of a division (a stored zero among them may carry the wrong sign without
+///  v_div_fixup).  `symbol_after_division`: inputs that hold such a value of an earlier segment.
+inline std::vector<bool> after_division(const item &it, const std::vector<bool> &symbol_after_division = {}) {
+    std::vector<bool> after(it.code.size(), false);
+    for (size_t i = 0; i < it.code.size(); i++) {
+        const gfir_instruction &c = it.code[i];
+        bool dependent = c.op == GFIR_DIV;
+        if (c.op == GFIR_INPUT && c.a < symbol_after_division.size() && symbol_after_division[c.a]) dependent = true;
+        for (const uint32_t o : it.operands(i)) dependent = dependent || after[o];
+        after[i] = dependent;
+    }
+    return after;
+}
+
+//------------------------------------------------------------------------------
+///  @brief Write the kernel text of an item, in the order in which it arrives.
+///
+///  @param[in] assembly The statement of the item's pass (asm_body.hpp, `ok`), for a `last` piece; else the compiled body.
+//------------------------------------------------------------------------------
+inline lowered write_item(const item &it, const codegen_options &opt, const piece_info &piece = piece_info(),
+                          const asm_body_text &assembly = asm_body_text()) {
     lowered out;
     const size_t esize = it.element_size();
 
@@ -890,11 +908,8 @@ inline lowered lower(const item &original, const codegen_options &opt = codegen_
     }
 
     const table_layout layout = layout_tables(it, opt);
-    const std::vector<int> &parent = layout.parent;
-    const std::vector<double> &factor = layout.factor;
-    const std::vector<uint32_t> &table_pack = layout.table_pack, &table_column = layout.table_column;
-    out.table_parent = parent;
-    out.table_factor = factor;
+    out.table_parent = layout.parent;
+    out.table_factor = layout.factor;
     out.packs = layout.packs;
     size_t lds_used = layout.lds_used;
     out.block_size = opt.block_size;
@@ -903,48 +918,22 @@ inline lowered lower(const item &original, const codegen_options &opt = codegen_
 //  shared reciprocals (guarded divisions may divide by zero on purpose), and the max of a complex
 //  output is the element of largest modulus, which reduce.hip finds.
     const bool generic = it.is_complex() || it.safe_math() || it.has_random();
+    const bool divides = std::any_of(it.code.begin(), it.code.end(), [] (const gfir_instruction &c) { return c.op == GFIR_DIV; });
+//  The statement stands in for the shared-reciprocal body: a pass that divides nothing has none.
+    const bool as_assembly = assembly.ok && divides;
     codegen_options plain = opt;
-    if (generic) plain.park_in_lds = false;
-//  The body as assembly (asm_body.hpp): only as the `last` piece of an item whose out-of-window lanes are redone by a
-//  separate launch — an IEEE function compiled into the kernel would claim registers beyond the 256 the pool ends at.
-    asm_body_text assembly;
-    const bool divides_at_all = std::any_of(it.code.begin(), it.code.end(), [] (const gfir_instruction &c) { return c.op == GFIR_DIV; });
-    if (opt.asm_body && piece.role == piece_role::last && !generic && divides_at_all && opt.division == division_mode::shared &&
-        it.code.size() >= opt.asm_min_nodes) {
-        const size_t per_block = 160u*1024u/opt.asm_waves;  // a workgroup of 256 lanes is one wave per SIMD of its CU
-        const uint32_t slot_limit = lds_used < per_block ? static_cast<uint32_t> ((per_block - lds_used)/(static_cast<size_t> (opt.block_size)*esize)) : 0;
-        asm_body_writer writer(it, opt, out.packs, parent, factor, table_pack, table_column, opt.block_size, slot_limit);
-        assembly = writer.write();
-        if (std::getenv("GFHIP_ASM_REPORT")) {
-            std::fprintf(stderr, "assembly body of %s: %s; %zu vector, %zu scalar, %zu table loads, %zu LDS reads, %zu LDS writes, %zu waits, %u slots\n",
-                         it.name.c_str(), assembly.ok ? "ok" : assembly.why.c_str(), assembly.vector, assembly.scalar, assembly.loads,
-                         assembly.lds_reads, assembly.lds_writes, assembly.waits, assembly.slots);
-        }
-    }
-    if (assembly.ok) plain.park_in_lds = false;
+    if (generic || as_assembly) plain.park_in_lds = false;
     uint32_t park_slots = 0;
     const std::vector<park_plan> plan = plain.park_in_lds && plain.park_capacity && piece.role != piece_role::redo
                                       ? plan_parking_belady(it, plain, lds_used, esize, park_slots)
                                       : plan_parking(it, plain, lds_used, esize, park_slots);
-    if (assembly.ok) park_slots = assembly.slots;
+    if (as_assembly) park_slots = assembly.slots;
     const size_t park_offset = lds_used;
     lds_used += static_cast<size_t> (park_slots)*opt.block_size*esize;
     out.lds_bytes = lds_used;
     out.park_slots = park_slots;
 
-//  Nodes that depend on the result of a division (a stored zero among them may carry the wrong
-//  sign without v_div_fixup), and whether the item divides at all.
-    std::vector<bool> after_division(it.code.size(), false);
-    bool divides = false;
-    for (size_t i = 0; i < it.code.size(); i++) {
-        const gfir_instruction &c = it.code[i];
-        const uint32_t operands[3] = {c.a, c.b, c.c};
-        bool dependent = c.op == GFIR_DIV;
-        if (c.op == GFIR_INPUT && c.a < piece.symbol_after_division.size() && piece.symbol_after_division[c.a]) dependent = true;
-        divides = divides || c.op == GFIR_DIV;
-        for (int k = 0; k < operand_count(c.op) && !dependent; k++) dependent = after_division[operands[k]];
-        after_division[i] = dependent;
-    }
+    const std::vector<bool> quotient = after_division(it, piece.symbol_after_division);
 
     std::ostringstream s;
     out.kernel_name = "gfhip_" + it.name;
@@ -953,10 +942,10 @@ inline lowered lower(const item &original, const codegen_options &opt = codegen_
 //  indices then divide by the literal scale).
 //  A segment that stores a quotient of an EARLIER segment has a zero to look at even if it divides nothing itself.
     bool stores_quotient = false;
-    for (auto &st : it.setters) stores_quotient = stores_quotient || after_division[st.value];
+    for (auto &st : it.setters) stores_quotient = stores_quotient || quotient[st.value];
     for (size_t o = 0; o < it.outputs.size(); o++) {
         const bool handed_over = o < piece.output_handed_over.size() && piece.output_handed_over[o];
-        stores_quotient = stores_quotient || (!handed_over && after_division[it.outputs[o]]);
+        stores_quotient = stores_quotient || (!handed_over && quotient[it.outputs[o]]);
     }
     const bool checks_needed = divides || (piece.role != piece_role::none && stores_quotient);
     const bool use_shared = opt.division != division_mode::ieee && checks_needed && !generic && piece.role != piece_role::redo;
@@ -973,11 +962,10 @@ inline lowered lower(const item &original, const codegen_options &opt = codegen_
     codegen_options resolved = opt;
     if (resolved.nontemporal < 0) resolved.nontemporal = it.code.size() >= 100 ? 1 : 0;
     const std::string no_assembly;
-    const bool as_assembly = assembly.ok && use_shared;
     if (as_assembly) resolved.waves_per_simd = opt.asm_waves;
     out.assembly = as_assembly;
-    kernel_writer writer{s, it, resolved, out, parent, factor, table_pack, table_column, plan, lds_used, park_offset, park_slots,
-                         use_shared, after_division, piece, as_assembly ? assembly.statement : no_assembly};
+    kernel_writer writer{s, it, resolved, out, layout.parent, layout.factor, layout.table_pack, layout.table_column, plan, lds_used,
+                         park_offset, park_slots, use_shared, quotient, piece, as_assembly ? assembly.statement : no_assembly};
     if (park_slots || as_assembly) s << "typedef __attribute__((address_space(3))) real park_t;\n";
     if (use_shared && piece.role == piece_role::none && opt.division != division_mode::fast) writer.ieee_function();
     writer.kernel(entry::plain);

@@ -30,9 +30,7 @@
 #include <vector>
 
 #include "../../include/gf_hip.h"
-#include "codegen.hpp"
-#include "merge.hpp"
-#include "segments.hpp"
+#include "plan.hpp"
 
 #include "converge_state.hpp"
 #include "superacc.hpp"
@@ -160,10 +158,11 @@ struct gfhip_context {
     }
 };
 
-//  One compiled kernel of a work item: the item itself, one segment of it (segments.hpp) or its redo launch.
-struct built_piece {
-    gfhip::segment plan;                           // a segment as an item, and what its symbols and outputs are
-    gfhip::lowered low;
+//  One compiled kernel of a work item: the item itself, one segment of it (segments.hpp) or its redo launch,
+//  as planned (`plan`: the piece as an item and what its symbols and outputs are; `low`: its text) and as loaded.
+struct built_piece : gfhip::planned_piece {
+    built_piece() = default;
+    explicit built_piece(gfhip::planned_piece &&planned) : gfhip::planned_piece(std::move(planned)) {}
     module_ptr module;
     hipFunction_t function = nullptr;
     hipFunction_t max_function = nullptr;          // `<name>_max`
@@ -298,100 +297,19 @@ extern "C" void gfhip_destroy_context(gfhip_context *ctx) {
     delete ctx;
 }
 
-//  How an item is compiled: as one kernel (`pieces` stays empty, `whole` is its lowering), or — items of
-//  more than options.segment_nodes records, or every large item when GFHIP_SEGMENTS asks for it — as a
-//  sequence of segment kernels (segments.hpp).  Returns the number of hand-over slots.
-static uint32_t plan_item(const gfhip::item &it, gfhip::lowered &whole, std::vector<built_piece> &pieces,
-                          std::optional<built_piece> *redo = nullptr) {
-    const gfhip::codegen_options opt = gfhip::codegen_options::from_environment();
-    size_t count = 1;
-    bool automatic = false;
-    if (gfhip::can_split(it)) {
-//  GFHIP_SEGMENTS=1: the item stays one kernel, but its lanes outside the window are redone by the redo launch
-//  instead of an IEEE function compiled into it (whose registers the kernel would have to reserve).
-        if (opt.segments >= 1 && it.code.size() >= opt.segments_min_nodes && it.code.size() >= 2*opt.segments) {
-            count = opt.segments;
-        } else if (opt.segment_nodes && it.code.size() > opt.segment_nodes) {
-            count = (it.code.size() + opt.segment_nodes - 1)/opt.segment_nodes;
-            automatic = true;
-        }
-    }
-//  GFHIP_ASM=1: the same one-kernel form for the items the assembly body takes (asm_body.hpp).
-    bool as_assembly = opt.asm_body && count < 2 && opt.segments == 0 && opt.schedule_for_pressure && gfhip::can_split(it) &&
-                       it.code.size() >= opt.asm_min_nodes && opt.division == gfhip::division_mode::shared &&
-                       gfhip::asm_body_writer::why_not(it, opt).empty();
-    gfhip::item ordered;
-    if (as_assembly) {
-//  ... if its values fit the register pool and the LDS slots in some emission order (lower() writes the statement of the
-//  piece below; here the same writer is asked whether it can).
-        std::vector<std::string> directories;
-        if (const char *env = std::getenv("GFHIP_CACHE_DIR")) directories.push_back(env);
-        directories.push_back(library_directory() + "/kernel_cache");
-        ordered = gfhip::schedule_for_assembly(it, opt, directories);
-        as_assembly = gfhip::assembly_fits(opt.merge ? gfhip::merge_records(ordered) : ordered, opt);
-    }
-    if (count < 2 && opt.segments != 1 && !as_assembly) {
-        whole = gfhip::lower(it, opt);
-        return 0;
-    }
-//  Cut in the pressure-aware emission order where that is affordable (schedule.hpp), else in the order given.
-    if (!as_assembly) ordered = opt.schedule_for_pressure ? gfhip::schedule_for_pressure(it) : it;
-//  Records that hold the same bits become one (merge.hpp), in emission order — the earliest is the one that is computed —
-//  and before the cut: hand-over slots carry representatives only.
-    if (opt.merge) {
-        gfhip::merge_report merges;
-        ordered = gfhip::merge_records(ordered, &merges);
-        if (std::getenv("GFHIP_ASM_REPORT")) merges.print(stderr, it.name);
-    }
-    gfhip::segmentation plan = gfhip::split_item(ordered, gfhip::choose_cuts(ordered, count));
-//  A one-kernel item keeps its name (profiles show gfhip_<name> and gfhip_<name>_redo).
-    if (plan.segments.size() == 1) plan.segments[0].piece.name = it.name;
-    gfhip::codegen_options piece_options = opt;
-//  Very large items are off the hot path: the compiler's division, no checks, no second body.
-    if (automatic) piece_options.division = gfhip::division_mode::ieee;
-//  The experiment on hot items keeps the shared-reciprocal division and compiles NO IEEE function into the
-//  segments (so that they fit two waves per SIMD): lanes outside the window are redone by one more launch.
-    const bool with_redo = !automatic && piece_options.division != gfhip::division_mode::ieee;
-//  Which values of the item depend on a quotient: a handed-over one keeps that mark in the segments that read it.
-    std::vector<bool> after_division(ordered.code.size(), false);
-    for (size_t i = 0; i < ordered.code.size(); i++) {
-        const gfir_instruction &c = ordered.code[i];
-        const uint32_t operands[3] = {c.a, c.b, c.c};
-        bool dependent = c.op == GFIR_DIV;
-        for (int k = 0; k < gfhip::operand_count(c.op) && !dependent; k++) dependent = after_division[operands[k]];
-        after_division[i] = dependent;
-    }
-    for (size_t p = 0; p < plan.segments.size(); p++) {
-        built_piece piece;
-        gfhip::piece_info role;
-        role.scheduled = opt.schedule_for_pressure;
-        if (with_redo) {
-            role.role = p + 1 == plan.segments.size() ? gfhip::piece_role::last : gfhip::piece_role::middle;
-            for (auto slot : plan.segments[p].output_slot) role.output_handed_over.push_back(slot >= 0);
-            for (auto record : plan.segments[p].symbol_record) role.symbol_after_division.push_back(record >= 0 && after_division[record]);
-        }
-        piece.low = gfhip::lower(plan.segments[p].piece, piece_options, role);
-        piece.plan = std::move(plan.segments[p]);
-        pieces.push_back(std::move(piece));
-    }
-    if (with_redo && redo) {
-        gfhip::piece_info role;
-        role.role = gfhip::piece_role::redo;
-        gfhip::codegen_options plain = opt;
-        plain.division = gfhip::division_mode::ieee;
-        plain.waves_per_simd = 0;
-        built_piece &r = redo->emplace();
-        r.plan.piece = it;                          // (lower() orders and merges it itself)
-        r.plan.piece.name = it.name + "_redo";
-        r.low = gfhip::lower(r.plan.piece, plain, role);
-    }
-    whole = gfhip::lowered();
-    whole.kernel_name = "gfhip_" + it.name;
-    whole.block_size = pieces[0].low.block_size;
-    whole.input_written.assign(it.symbols.size(), false);
-    for (auto &s : it.setters) whole.input_written[s.input] = true;
-    for (auto &piece : pieces) whole.hash = whole.hash*1099511628211ull ^ piece.low.hash;
-    return plan.slots;
+//  Where code objects, and the emission orders the assembly search chose, are looked for: GFHIP_CACHE_DIR, then the package.
+static std::vector<std::string> cache_directories() {
+    std::vector<std::string> directories;
+    if (const char *env = std::getenv("GFHIP_CACHE_DIR")) directories.push_back(env);
+    directories.push_back(library_directory() + "/kernel_cache");
+    return directories;
+}
+
+//  Parse an item and plan its lowering (plan.hpp) under the options of the environment, read here once per entry point.
+static bool parse_and_plan(const void *gfir, const size_t bytes, gfhip::item &it, gfhip::item_plan &plan, std::string &error) {
+    if (!it.parse(gfir, bytes, error)) return false;
+    plan = gfhip::plan_item(it, gfhip::codegen_options::from_environment(), cache_directories());
+    return true;
 }
 
 extern "C" gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, size_t bytes, size_t num_rays) {
@@ -399,19 +317,16 @@ extern "C" gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, 
     std::unique_ptr<gfhip_kernel> k(new gfhip_kernel);
     k->ctx = ctx;
     k->num_rays = num_rays;
-    if (!k->item.parse(gfir, bytes, ctx->error)) {
+    gfhip::item_plan plan;
+    if (!parse_and_plan(gfir, bytes, k->item, plan, ctx->error)) {
         return nullptr;
     }
-    const uint32_t slots = plan_item(k->item, k->whole.low, k->pieces, &k->redo);
+    k->whole.low = std::move(plan.whole);
+    for (auto &piece : plan.pieces) k->pieces.emplace_back(std::move(piece));
+    if (plan.redo) k->redo.emplace(std::move(*plan.redo));
     if (!k->pieces.empty()) {
-//  Rays per walk of the segment sequence: the hand-over buffers of one chunk stay in the Infinity Cache.
-        const gfhip::codegen_options opt = gfhip::codegen_options::from_environment();
-        size_t chunk = opt.handover_bytes/(static_cast<size_t> (slots ? slots : 1)*k->item.element_size());
-        chunk = chunk/1024*1024;
-        if (chunk < 16384) chunk = 16384;
-        k->chunk = num_rays < chunk ? num_rays : chunk;
-        if (slots == 0) k->chunk = num_rays;         // one piece (the assembly body): nothing is handed over, one walk over all rays
-        k->handover.resize(slots);
+        k->chunk = plan.chunk(num_rays, k->item.element_size());
+        k->handover.resize(plan.slots);
     }
     ctx->kernels.push_back(std::move(k));
     return ctx->kernels.back().get();
@@ -419,21 +334,15 @@ extern "C" gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, 
 
 extern "C" int gfhip_export_piece(const void *gfir, size_t bytes, uint32_t index, void **piece, size_t *piece_bytes) {
     gfhip::item it;
-    std::string error;
+    gfhip::item_plan planned;
     if (!piece || !piece_bytes) return 1;
     *piece = nullptr;
     *piece_bytes = 0;
-    if (!it.parse(gfir, bytes, error)) {
-        creation_error = error;
-        return 1;
-    }
-    gfhip::lowered whole;
-    std::vector<built_piece> pieces;
-    const uint32_t slots = plan_item(it, whole, pieces);
-    if (index >= pieces.size()) return 0;
-    const gfhip::segment &plan = pieces[index].plan;
+    if (!parse_and_plan(gfir, bytes, it, planned, creation_error)) return 1;
+    if (index >= planned.pieces.size()) return 0;
+    const gfhip::segment &plan = planned.pieces[index].plan;
     std::vector<int32_t> head = {static_cast<int32_t> (plan.piece.symbols.size()), static_cast<int32_t> (plan.piece.outputs.size()),
-                                 static_cast<int32_t> (slots), static_cast<int32_t> (pieces.size())};
+                                 static_cast<int32_t> (planned.slots), static_cast<int32_t> (planned.pieces.size())};
     head.insert(head.end(), plan.symbol_state.begin(), plan.symbol_state.end());
     head.insert(head.end(), plan.symbol_slot.begin(), plan.symbol_slot.end());
     head.insert(head.end(), plan.output_slot.begin(), plan.output_slot.end());
@@ -448,24 +357,17 @@ extern "C" int gfhip_export_piece(const void *gfir, size_t bytes, uint32_t index
 
 extern "C" int gfhip_generate_piece_source(const void *gfir, size_t bytes, uint32_t index, char **source, uint64_t *source_hash) {
     gfhip::item it;
-    std::string error;
+    gfhip::item_plan plan;
     if (!source) return 1;
     *source = nullptr;
-    if (!it.parse(gfir, bytes, error)) {
-        creation_error = error;
-        return 1;
-    }
-    gfhip::lowered whole;
-    std::vector<built_piece> pieces;
-    std::optional<built_piece> redo;
-    (void)plan_item(it, whole, pieces, &redo);
+    if (!parse_and_plan(gfir, bytes, it, plan, creation_error)) return 1;
     const gfhip::lowered *low = nullptr;
-    if (pieces.empty()) {
-        if (index == 0) low = &whole;
-    } else if (index < pieces.size()) {
-        low = &pieces[index].low;
-    } else if (redo && index == pieces.size()) {
-        low = &redo->low;
+    if (plan.pieces.empty()) {
+        if (index == 0) low = &plan.whole;
+    } else if (index < plan.pieces.size()) {
+        low = &plan.pieces[index].low;
+    } else if (plan.redo && index == plan.pieces.size()) {
+        low = &plan.redo->low;
     }
     if (!low) return 0;                                 // past the last piece: *source stays NULL
     if (source_hash) *source_hash = low->hash;
@@ -476,21 +378,16 @@ extern "C" int gfhip_generate_piece_source(const void *gfir, size_t bytes, uint3
 
 extern "C" char *gfhip_generate_source(const void *gfir, size_t bytes, uint64_t *source_hash) {
     gfhip::item it;
-    std::string error;
-    if (!it.parse(gfir, bytes, error)) {
-        creation_error = error;
-        return nullptr;
-    }
-    gfhip::lowered low;
-    std::vector<built_piece> pieces;
-    (void)plan_item(it, low, pieces);
-//  A segmented item: the texts of its pieces one after the other (each is a translation unit of its
+    gfhip::item_plan plan;
+    if (!parse_and_plan(gfir, bytes, it, plan, creation_error)) return nullptr;
+//  An item in pieces: the texts of its pieces one after the other (each is a translation unit of its
 //  own: gfhip_generate_piece_source hands them out one by one).
-    for (auto &piece : pieces) low.source += piece.low.source;
-    if (source_hash) *source_hash = low.hash;
-    char *text = static_cast<char *> (std::malloc(low.source.size() + 1));
-    std::memcpy(text, low.source.c_str(), low.source.size() + 1);
-    return text;
+    std::string text = plan.whole.source;
+    for (auto &piece : plan.pieces) text += piece.low.source;
+    if (source_hash) *source_hash = plan.whole.hash;
+    char *copy = static_cast<char *> (std::malloc(text.size() + 1));
+    std::memcpy(copy, text.c_str(), text.size() + 1);
+    return copy;
 }
 
 extern "C" void gfhip_free_string(char *text) {
@@ -501,12 +398,8 @@ extern "C" void gfhip_free_string(char *text) {
 static int load_code_object(gfhip_context *ctx, const std::string &name, const gfhip::lowered &low,
                             std::vector<char> &code, bool &from_cache) {
     const std::string file = hash_name(low.hash) + ".hsaco";
-    std::vector<std::string> directories;
-    if (const char *env = std::getenv("GFHIP_CACHE_DIR")) directories.push_back(env);
-    directories.push_back(library_directory() + "/kernel_cache");
-
     from_cache = false;
-    for (auto &d : directories) {
+    for (auto &d : cache_directories()) {
         if (read_file(d + "/" + file, code)) {
             from_cache = true;
             return 0;

@@ -20,6 +20,25 @@ struct table {
     std::vector<double> data;               ///< rows*cols values (complex items: (re, im) pairs)
 };
 
+///  How many of a record's fields a, b, c name records it reads.
+inline int operand_count(const uint32_t op) {
+    switch (op) {
+        case GFIR_CONST: case GFIR_INPUT: return 0;
+        case GFIR_FMA: return 3;
+        case GFIR_SQRT: case GFIR_POWI: case GFIR_SIN: case GFIR_COS: case GFIR_EXP: case GFIR_LOG: case GFIR_ERFI:
+        case GFIR_GATHER1: case GFIR_INDEX1: case GFIR_RANDOM: return 1;
+        default: return 2;
+    }
+}
+
+///  The records one record reads, to iterate over.
+struct operand_list {
+    uint32_t record[3];
+    int count;
+    const uint32_t *begin() const { return record; }
+    const uint32_t *end() const { return record + count; }
+};
+
 struct item {
     uint32_t dtype = GFIR_F64;
     uint32_t flags = 0;                     ///< GFIR_SAFE_MATH
@@ -33,6 +52,12 @@ struct item {
                                             ///< empty when nothing is merged.  Not part of the serialized item.
 
     bool is_merged(const size_t record) const { return !merged_into.empty() && merged_into[record] != GFIR_NONE; }
+///  The operands of a record as they are written in it (a merged record is a copy of its representative: who treats it
+///  as reading nothing asks is_merged() first).
+    operand_list operands(const size_t record) const {
+        const gfir_instruction &c = code[record];
+        return {{c.a, c.b, c.c}, operand_count(c.op)};
+    }
 
     static size_t element_size(const uint32_t dtype) {
         return dtype == GFIR_F32 ? 4 : dtype == GFIR_C64 ? 16 : 8;

@@ -38,7 +38,6 @@
 #include <vector>
 
 #include "gfir_item.hpp"
-#include "schedule.hpp"
 
 namespace gfhip {
 

@@ -3,6 +3,9 @@
 ///  @brief Knobs of the lowering (defaults are the measured best; every override changes the
 ///  generated text and therefore the kernel-cache key), the cache hash and the compile flags.
 ///
+///  The lowering takes its options as a parameter (plan.hpp); the environment is read by the
+///  entry points of the C ABI, once each.
+///
 ///  Alternatives that were measured neutral or slower on MI355X (packed fp32 pairs, 2/4 rays per
 ///  lane, next-tile prefetch, pipelined tiles, scheduling fences, explicit order files) are
 ///  recorded in DESIGN.md and are no longer part of the lowering.
@@ -70,7 +73,7 @@ struct codegen_options {
     size_t handover_bytes = 128u << 20; ///< the hand-over buffers of a segmented item hold one chunk of rays and at most this many
                                         ///< bytes, so that they stay in the 256 MB Infinity Cache (GFHIP_HANDOVER_BYTES)
 
-//  Environment overrides (they change the generated text, hence the cache key).
+//  Environment overrides (they change the generated text, hence the cache key): for the entry points of gf_hip.cpp.
     static codegen_options from_environment() {
         codegen_options o;
         if (const char *e = std::getenv("GFHIP_DIVISION")) {

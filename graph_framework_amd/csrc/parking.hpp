@@ -15,7 +15,6 @@
 
 #include "gfir_item.hpp"
 #include "options.hpp"
-#include "schedule.hpp"
 
 namespace gfhip {
 
@@ -48,12 +47,9 @@ inline std::vector<park_plan> plan_parking(const item &it, const codegen_options
                               : 0;
     if (opt.park_in_lds && slot_limit > 0) {
         std::vector<std::vector<size_t>> uses(node_count);
-        auto arity = [] (const uint32_t op) -> int { return operand_count(op); };
         for (size_t i = 0; i < node_count; i++) {
-            const gfir_instruction &c = it.code[i];
-            const uint32_t operands[3] = {c.a, c.b, c.c};
-            for (int k = 0; k < arity(c.op); k++) {
-                if (uses[operands[k]].empty() || uses[operands[k]].back() != i) uses[operands[k]].push_back(i);
+            for (const uint32_t o : it.operands(i)) {
+                if (uses[o].empty() || uses[o].back() != i) uses[o].push_back(i);
             }
         }
         for (auto &st : it.setters) uses[st.value].push_back(node_count);
@@ -120,10 +116,8 @@ inline std::vector<park_plan> plan_parking_belady(const item &it, const codegen_
     const size_t never = static_cast<size_t> (1) << 60;
     std::vector<std::vector<size_t>> uses(n);
     for (size_t i = 0; i < n; i++) {
-        const gfir_instruction &c = it.code[i];
-        const uint32_t operands[3] = {c.a, c.b, c.c};
-        for (int k = 0; k < operand_count(c.op); k++) {
-            if (uses[operands[k]].empty() || uses[operands[k]].back() != i) uses[operands[k]].push_back(i);
+        for (const uint32_t o : it.operands(i)) {
+            if (uses[o].empty() || uses[o].back() != i) uses[o].push_back(i);
         }
     }
     for (auto &st : it.setters) uses[st.value].push_back(n);
@@ -176,10 +170,9 @@ inline std::vector<park_plan> plan_parking_belady(const item &it, const codegen_
     for (size_t p = 0; p < n; p++) {
         const gfir_instruction &c = it.code[p];
         if (c.op == GFIR_CONST) continue;
-        const uint32_t operands[3] = {c.a, c.b, c.c};
         std::set<uint32_t> needed;
-        for (int k = 0; k < operand_count(c.op); k++) {
-            if (is_value(operands[k])) needed.insert(operands[k]);
+        for (const uint32_t o : it.operands(p)) {
+            if (is_value(o)) needed.insert(o);
         }
         for (const uint32_t o : needed) {
             if (!resident.count(o)) {

@@ -17,11 +17,12 @@
 ///
 ///  A segment is an ordinary item: its symbols are the state inputs it reads plus one input per
 ///  handed-over value it uses, its outputs are the values it hands over (the last segment: the item's
-///  setters and outputs), and it is lowered by the same kernel_writer.  The state arrays are written by
+///  setters and outputs), and it is written by the same kernel_writer.  The state arrays are written by
 ///  the last segment only, so every segment reads the state of the beginning of the pass.  Hand-over
 ///  buffers are SoA arrays of one chunk of rays; a slot is reused once its value has been read for the
 ///  last time.  The host walks the ensemble in chunks sized so that the hand-over buffers stay in the
-///  256 MB Infinity Cache (gf_hip.cpp).
+///  256 MB Infinity Cache (plan.hpp: item_plan::chunk).  This file only cuts: which item is cut, into
+///  how many segments and in which role each is written is plan.hpp's.
 //------------------------------------------------------------------------------
 #ifndef gfhip_segments_hpp
 #define gfhip_segments_hpp
@@ -36,8 +37,6 @@
 #include <vector>
 
 #include "gfir_item.hpp"
-#include "options.hpp"
-#include "schedule.hpp"
 
 namespace gfhip {
 
@@ -81,9 +80,8 @@ inline std::vector<size_t> choose_cuts(const item &it, const size_t count, const
     const size_t n = it.code.size();
     std::vector<size_t> last_use(n, 0);
     for (size_t i = 0; i < n; i++) {
-        const gfir_instruction &c = it.code[i];
-        const uint32_t operands[3] = {c.a, c.b, c.c};
-        for (int k = 0; k < operand_count(c.op) && !it.is_merged(i); k++) last_use[operands[k]] = i;    // (a merged record reads nothing)
+        if (it.is_merged(i)) continue;                  // (a merged record reads nothing)
+        for (const uint32_t o : it.operands(i)) last_use[o] = i;
     }
     for (auto &s : it.setters) last_use[s.value] = n;
     for (auto o : it.outputs) last_use[o] = n;
@@ -150,9 +148,8 @@ inline segmentation split_item(const item &it, const std::vector<size_t> &cuts) 
         return it.is_merged(i) && segment_of(it.merged_into[i]) == segment_of(i);
     };
     for (size_t i = 0; i < n; i++) {
-        const gfir_instruction &c = it.code[i];
-        const uint32_t operands[3] = {c.a, c.b, c.c};
-        for (int k = 0; k < operand_count(c.op) && !it.is_merged(i); k++) use(operands[k], segment_of(i));
+        if (it.is_merged(i)) continue;
+        for (const uint32_t o : it.operands(i)) use(o, segment_of(i));
     }
     for (auto &s : it.setters) use(s.value, count - 1);
     for (auto o : it.outputs) use(o, count - 1);

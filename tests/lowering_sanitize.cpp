@@ -1,7 +1,8 @@
 // Host-only driver for the GFIR parser, scheduler and lowering (no HIP runtime): built with
 // -fsanitize=address,undefined by tests/test_cabi.py and run over every exported workload and
 // over mutated items; every item that can be split is also cut into 2..5 segments (csrc/segments.hpp), each segment
-// serialized, parsed again and lowered in the roles of a split with a redo launch.
+// serialized, parsed again and lowered in the roles of a split with a redo launch.  Every item that parses also goes through
+// plan_item() itself (csrc/plan.hpp, what libgf_hip.so calls) under three sets of options.
 // Usage: lowering_sanitize <file.gfir>... [--mutate seed trials file.gfir]
 #include <cstdio>
 #include <cstdlib>
@@ -12,20 +13,42 @@
 #include <vector>
 
 #include "../include/gfir.h"
-#include "../graph_framework_amd/csrc/codegen.hpp"
-#include "../graph_framework_amd/csrc/segments.hpp"
+#include "../graph_framework_amd/csrc/plan.hpp"
 
 static std::vector<char> read_file(const char *path) {
     std::ifstream f(path, std::ios::binary);
     return std::vector<char> ((std::istreambuf_iterator<char> (f)), std::istreambuf_iterator<char> ());
 }
 
+//  The shipped planning code: the defaults, three segments, and the assembly body whatever the size.
+static uint64_t plan_hash(const gfhip::item &it) {
+    gfhip::codegen_options three, assembly;
+    three.segments = 3;
+    three.segments_min_nodes = 40;
+    assembly.asm_min_nodes = 0;
+    assembly.asm_schedule_tries = 3;
+    uint64_t hash = 0;
+    for (const gfhip::codegen_options &opt : {gfhip::codegen_options(), three, assembly}) {
+        const gfhip::item_plan plan = gfhip::plan_item(it, opt, {});
+        hash ^= plan.whole.hash ^ plan.chunk(100000, it.element_size());
+        for (auto &piece : plan.pieces) hash ^= piece.low.hash;
+        if (plan.redo) hash ^= plan.redo->low.hash;
+    }
+    return hash;
+}
+
+//  What plan_item() hands the writer for a `last` piece: the statement, if the piece is a candidate for one.
+static gfhip::asm_body_text statement_of(const gfhip::item &piece, const gfhip::codegen_options &opt, const gfhip::piece_info &role) {
+    const bool offered = role.role == gfhip::piece_role::last && gfhip::assembly_candidate(piece, opt);
+    return offered ? gfhip::assembly_statement(piece, opt) : gfhip::asm_body_text();
+}
+
 static bool lower_bytes(const std::vector<char> &bytes, uint64_t &hash) {
     gfhip::item it;
     std::string error;
     if (!it.parse(bytes.data(), bytes.size(), error)) return false;
-    const gfhip::lowered low = gfhip::lower(it);
-    hash = low.hash;
+    const gfhip::codegen_options defaults;
+    hash = gfhip::write_item(gfhip::in_emission_order(it, defaults), defaults).hash ^ plan_hash(it);
     if (gfhip::can_split(it) && it.code.size() >= 40 && it.code.size() < 20000) {
         const gfhip::item ordered = gfhip::schedule_for_pressure(it);
         for (size_t count = 2; count <= 5; count++) {
@@ -40,7 +63,8 @@ static bool lower_bytes(const std::vector<char> &bytes, uint64_t &hash) {
                 gfhip::piece_info role;
                 role.role = p + 1 == plan.segments.size() ? gfhip::piece_role::last : gfhip::piece_role::middle;
                 for (auto slot : plan.segments[p].output_slot) role.output_handed_over.push_back(slot >= 0);
-                hash ^= gfhip::lower(again, gfhip::codegen_options(), role).hash;
+                const gfhip::item piece = gfhip::schedule_for_pressure(again);
+                hash ^= gfhip::write_item(piece, defaults, role, statement_of(piece, defaults, role)).hash;
             }
         }
 //  The whole item as one piece whose pass is the assembly body (csrc/asm_body.hpp), whatever its size: the order search
@@ -54,14 +78,13 @@ static bool lower_bytes(const std::vector<char> &bytes, uint64_t &hash) {
             const gfhip::item chosen = gfhip::schedule_for_assembly(it, assembly);
             gfhip::piece_info whole;
             whole.role = gfhip::piece_role::last;
-            whole.scheduled = true;
-            hash ^= gfhip::lower(chosen, assembly, whole).hash;
+            hash ^= gfhip::write_item(chosen, assembly, whole, statement_of(chosen, assembly, whole)).hash;
         }
         gfhip::piece_info redo;
         redo.role = gfhip::piece_role::redo;
         gfhip::codegen_options plain;
         plain.division = gfhip::division_mode::ieee;
-        hash ^= gfhip::lower(it, plain, redo).hash;
+        hash ^= gfhip::write_item(gfhip::in_emission_order(it, plain), plain, redo).hash;
     }
     return true;
 }

@@ -2,7 +2,8 @@
 // tests/test_merge.py and run over every exported workload and over mutated items.  Every item that parses is merged in the
 // order it arrives in and in the pressure-aware order; what the pass returns is held to its contract (a merged record is a
 // copy of an earlier, unmerged record; nothing reads a merged record), ordered again, cut into 2..4 segments, and written by
-// both kernel writers.
+// both kernel writers.  Every item that parses also goes through plan_item() itself (csrc/plan.hpp, what libgf_hip.so
+// calls) under three sets of options.
 // Usage: merge_sanitize <file.gfir>... [--mutate seed trials file.gfir]
 #include <cstdio>
 #include <cstdlib>
@@ -13,9 +14,7 @@
 #include <vector>
 
 #include "../include/gfir.h"
-#include "../graph_framework_amd/csrc/codegen.hpp"
-#include "../graph_framework_amd/csrc/merge.hpp"
-#include "../graph_framework_amd/csrc/segments.hpp"
+#include "../graph_framework_amd/csrc/plan.hpp"
 
 static std::vector<char> read_file(const char *path) {
     std::ifstream f(path, std::ios::binary);
@@ -34,10 +33,9 @@ static void check(const gfhip::item &before, const gfhip::item &after, const gfh
     size_t merged = 0;
     for (size_t i = 0; i < n; i++) {
         const gfir_instruction &c = after.code[i];
-        const uint32_t operands[3] = {c.a, c.b, c.c};
-        for (int k = 0; k < gfhip::operand_count(c.op); k++) {
-            if (operands[k] >= i) fail("an operand is not an earlier record", i);
-            if (after.is_merged(operands[k])) fail("a merged record is read", i);
+        for (const uint32_t o : after.operands(i)) {
+            if (o >= i) fail("an operand is not an earlier record", i);
+            if (after.is_merged(o)) fail("a merged record is read", i);
         }
         if (!after.is_merged(i)) continue;
         merged++;
@@ -50,6 +48,34 @@ static void check(const gfhip::item &before, const gfhip::item &after, const gfh
     if (merged != report.records() || merged != report.merged.size()) fail("the report counts other merges", merged);
 }
 
+//  The shipped planning code: the defaults, three segments, and the assembly body whatever the size.
+static uint64_t plan_hash(const gfhip::item &it) {
+    gfhip::codegen_options three, assembly;
+    three.segments = 3;
+    three.segments_min_nodes = 40;
+    assembly.asm_min_nodes = 0;
+    assembly.asm_schedule_tries = 3;
+    uint64_t hash = 0;
+    for (const gfhip::codegen_options &opt : {gfhip::codegen_options(), three, assembly}) {
+        const gfhip::item_plan plan = gfhip::plan_item(it, opt, {});
+        for (auto &piece : plan.pieces) {
+            const gfhip::item &part = piece.plan.piece;
+            for (size_t i = 0; i < part.code.size(); i++) {
+                if (part.is_merged(i) && (part.merged_into[i] >= i || part.is_merged(part.merged_into[i]))) fail("a planned piece names a later record", i);
+            }
+            hash ^= piece.low.hash;
+        }
+        hash ^= plan.whole.hash ^ (plan.redo ? plan.redo->low.hash : 0);
+    }
+    return hash;
+}
+
+//  What plan_item() hands the writer for a `last` piece: the statement, if the piece is a candidate for one.
+static gfhip::asm_body_text statement_of(const gfhip::item &piece, const gfhip::codegen_options &opt, const gfhip::piece_info &role) {
+    const bool offered = role.role == gfhip::piece_role::last && gfhip::assembly_candidate(piece, opt);
+    return offered ? gfhip::assembly_statement(piece, opt) : gfhip::asm_body_text();
+}
+
 static bool merge_bytes(const std::vector<char> &bytes, size_t &merged) {
     gfhip::item it;
     std::string error;
@@ -58,7 +84,8 @@ static bool merge_bytes(const std::vector<char> &bytes, size_t &merged) {
     const gfhip::item in_source_order = gfhip::merge_records(it, &report);
     check(it, in_source_order, report);
     merged += report.records();
-    if (it.code.size() >= 20000) return true;           // (the 54 k-record VMEC step: the pass and its contract only)
+    uint64_t hash = plan_hash(it);
+    if (it.code.size() >= 20000) return hash != 1;      // (the 54 k-record VMEC step: the pass, its contract and its plan only)
     const gfhip::item ordered = gfhip::schedule_for_pressure(it);
     const gfhip::item merged_item = gfhip::merge_records(ordered, &report);
     check(ordered, merged_item, report);
@@ -71,7 +98,8 @@ static bool merge_bytes(const std::vector<char> &bytes, size_t &merged) {
     for (size_t i = 0; i < reordered.code.size(); i++) {
         if (reordered.is_merged(i) && reordered.merged_into[i] >= i) fail("a merged record is ordered before its representative", i);
     }
-    uint64_t hash = gfhip::lower(it).hash;               // (lower() orders and merges a whole item itself)
+    const gfhip::codegen_options defaults;
+    hash ^= gfhip::write_item(gfhip::in_emission_order(it, defaults), defaults).hash;
     if (gfhip::can_split(it) && it.code.size() >= 40) {
         for (size_t count = 2; count <= 4; count++) {
             gfhip::segmentation plan = gfhip::split_item(merged_item, gfhip::choose_cuts(merged_item, count));
@@ -82,9 +110,8 @@ static bool merge_bytes(const std::vector<char> &bytes, size_t &merged) {
                 }
                 gfhip::piece_info role;
                 role.role = p + 1 == plan.segments.size() ? gfhip::piece_role::last : gfhip::piece_role::middle;
-                role.scheduled = true;
                 for (auto slot : plan.segments[p].output_slot) role.output_handed_over.push_back(slot >= 0);
-                hash ^= gfhip::lower(piece, gfhip::codegen_options(), role).hash;
+                hash ^= gfhip::write_item(piece, defaults, role, statement_of(piece, defaults, role)).hash;
             }
         }
 //  the whole item as one piece whose pass is the assembly body, with a small register pool
@@ -97,8 +124,7 @@ static bool merge_bytes(const std::vector<char> &bytes, size_t &merged) {
             const gfhip::item chosen = gfhip::merge_records(gfhip::schedule_for_assembly(it, assembly));
             gfhip::piece_info whole;
             whole.role = gfhip::piece_role::last;
-            whole.scheduled = true;
-            hash ^= gfhip::lower(chosen, assembly, whole).hash;
+            hash ^= gfhip::write_item(chosen, assembly, whole, statement_of(chosen, assembly, whole)).hash;
         }
     }
     return hash != 1;
