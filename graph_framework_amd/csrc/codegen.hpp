@@ -839,7 +839,9 @@ struct kernel_writer {
 
 //  Epilogue of create_max_call: 64-lane shuffle reduction, one LDS word per wave, ONE
 //  device-scope atomicMax per workgroup on an order-preserving integer image of the value
-//  (max is exact and order independent: the same bits as a serial scan).
+//  (max is exact and order independent: the maximum of a serial scan as a number — the same bits
+//  unless it is a zero, where the image prefers +0 and a scan keeps the first of -0 and +0, and a
+//  canonical NaN for a NaN at element 0).
     void max_epilogue(const std::string &lane, const std::string &target, const std::string &scratch) {
         const char *bits = f64 ? "unsigned long long" : "unsigned int";
         s << "    for (int offset = 32; offset > 0; offset >>= 1) {\n"

@@ -958,6 +958,14 @@ static int converge_loop(gfhip_kernel *k, const double tolerance_, const size_t 
     return 0;
 }
 
+//  std::abs of a complex value as the reference's build has it: the C library's cabs, that is hypot.  In a HIP
+//  translation unit std::abs(std::complex) is the textbook scaled formula instead (the compiler's complex wrapper
+//  turns the C99 functions off): NaN for an infinite part, and not always hypot's last bit.
+template<typename B>
+static B modulus(const std::complex<B> &z) {
+    return std::hypot(z.real(), z.imag());
+}
+
 //  ... for complex items (max = the element of largest modulus; the loop compares moduli,
 //  workflow.hpp:183-186 with T = std::complex).
 template<typename B>
@@ -971,9 +979,9 @@ static int converge_loop_complex(gfhip_kernel *k, const double tolerance_, const
     T max_residual(static_cast<B> (value[0]), static_cast<B> (value[1]));
     T last = std::numeric_limits<T>::max();            // std::numeric_limits<std::complex> is the unspecialised one: T()
     T off_last = std::numeric_limits<T>::max();
-    while (std::abs(max_residual) > std::abs(tolerance)            &&
-           std::abs(last - max_residual) > std::abs(tolerance)     &&
-           std::abs(off_last - max_residual) > std::abs(tolerance) &&
+    while (modulus(max_residual) > modulus(tolerance)            &&
+           modulus(last - max_residual) > modulus(tolerance)     &&
+           modulus(off_last - max_residual) > modulus(tolerance) &&
            iterations++ < max_iterations) {
         last = max_residual;
         if (!(iterations%2)) {
@@ -983,7 +991,7 @@ static int converge_loop_complex(gfhip_kernel *k, const double tolerance_, const
         max_residual = T(static_cast<B> (value[0]), static_cast<B> (value[1]));
     }
     if (iterations_out) *iterations_out = iterations;
-    if (last_max) *last_max = static_cast<double> (std::abs(max_residual));
+    if (last_max) *last_max = static_cast<double> (modulus(max_residual));
     return 0;
 }
 

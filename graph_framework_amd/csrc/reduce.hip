@@ -9,7 +9,11 @@
 ///  a 64-lane wavefront reduction with __shfl_down (no LDS traffic), one LDS
 ///  word per wave, and ONE device-scope atomicMax per workgroup on an
 ///  order-preserving integer image of the value.  max is exact and order
-///  independent, so the result is bit-identical to a serial scan.
+///  independent, so the result is the maximum a serial scan finds, as a number:
+///  the same bits unless it is a zero (-0 and +0 are equal; a scan keeps the first
+///  of them, the integer image prefers +0, and which one a lane or a wave hands on
+///  depends on the grid), and a canonical NaN, not the element's payload, when
+///  element 0 is a NaN (the only place where std::max_element selects one).
 ///  HBM-bound: 8 (4) bytes per element, one pass.
 //------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
@@ -224,8 +228,11 @@ max_modulus_kernel(const complex_pair<T> *__restrict__ in, const unsigned long l
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-//  std::max_element keeps element 0 when every comparison is false (all moduli NaN).
-        *result = in[places[0] < n ? places[0] : 0];
+//  std::max_element keeps element 0 when every comparison is false: all moduli NaN, or the modulus of
+//  element 0 a NaN whatever follows (`abs(in[0]) < abs(x)` is never true) — as first_is_nan above.
+        const T first = sizeof(T) == 8 ? static_cast<T> (hypot(static_cast<double> (in[0].re), static_cast<double> (in[0].im)))
+                                       : static_cast<T> (hypotf(static_cast<float> (in[0].re), static_cast<float> (in[0].im)));
+        *result = in[places[0] < n && first == first ? places[0] : 0];
     }
 }
 

@@ -57,6 +57,18 @@ def erfi(z):
     return complex(out[0], out[1])
 
 
+def max_element(values):
+    """Index std::max_element returns (cpu_context.hpp:306-322): `m < x` for real values, `abs(m) < abs(x)`
+    in the base precision for complex ones.  The first of equals wins, -0 and +0 are equal, and a NaN,
+    for which every comparison is false, is selected only as element 0 — where it stays whatever follows."""
+    values = np.asarray(values)
+    with np.errstate(all="ignore"):
+        key = np.abs(values) if np.iscomplexobj(values) else values
+    if key.size == 0 or np.isnan(key[0]):
+        return 0
+    return int(np.argmax(np.where(np.isnan(key), -np.inf, key)))
+
+
 class Item:
     """One work item executed on the CPU exactly as gpu::cpu_context's kernel loop would."""
 
@@ -143,34 +155,33 @@ class Item:
 
     def converge(self, columns, tolerance=1.0e-30, max_iterations=1000):
         """workflow::converge_item::run (workflow.hpp:179-205): repeat the kernel until the
-        max of its last output stalls.  Returns (iterations, last max, outputs)."""
+        max of its last output stalls.  Returns (iterations, last max, outputs).  Every value and
+        every comparison is in the item's own type, as in the reference (tests/max_model.py is the
+        same loop on scripted maxima; tests/test_max_model.py holds the two equal)."""
+        kind = self.np_dtype
+        outs = None
+
         def max_kernel():
+            nonlocal outs
             outs, _ = self.run(columns)
             values = outs[-1]
-            if np.iscomplexobj(values):
-#  complex items: the element of largest modulus, the first of equals (cpu_context.hpp:314-318)
-                return complex(values[int(np.argmax(np.abs(values)))]), outs
-#  std::max_element (cpu_context.hpp:306-322): `m < x` is false for NaN, so a NaN is never
-#  selected unless it is the first element.
-            if np.isnan(values[0]):
-                return float("nan"), outs
-            return float(np.fmax.reduce(values)), outs
+            return kind(values[max_element(values)])
 
-        big = float(np.finfo(self.np_dtype).max)
-        iterations = 0
-        max_residual, outs = max_kernel()
-        if isinstance(max_residual, complex):
-            big = 0.0j                               # std::numeric_limits<std::complex<T>>::max() is T()
-        last_max = big
-        off_last_max = big
-        while (abs(max_residual) > abs(tolerance) and abs(last_max - max_residual) > abs(tolerance)
-               and abs(off_last_max - max_residual) > abs(tolerance)):
-            took = iterations < max_iterations
-            iterations += 1
-            if not took:
-                break
-            last_max = max_residual
-            if not iterations % 2:
-                off_last_max = max_residual
-            max_residual, outs = max_kernel()
-        return iterations, max_residual, outs
+        with np.errstate(all="ignore"):
+            tol = abs(kind(tolerance))
+#  std::numeric_limits<std::complex<T>>::max() is the unspecialised one: T()
+            big = kind(0) if np.iscomplexobj(kind(0)) else kind(np.finfo(kind).max)
+            last_max = off_last_max = big
+            iterations = 0
+            max_residual = max_kernel()
+            while (abs(max_residual) > tol and abs(kind(last_max - max_residual)) > tol
+                   and abs(kind(off_last_max - max_residual)) > tol):
+                took = iterations < max_iterations
+                iterations += 1
+                if not took:
+                    break
+                last_max = max_residual
+                if not iterations % 2:
+                    off_last_max = max_residual
+                max_residual = max_kernel()
+        return iterations, (complex(max_residual) if np.iscomplexobj(max_residual) else float(max_residual)), outs
