@@ -1,7 +1,8 @@
 //------------------------------------------------------------------------------
 ///  @file tables.hpp
 ///  @brief Where the coefficient tables of a work item live: exact compaction (tables that are a
-///  constant multiple of another are not stored), AoS packs per table shape, LDS staging.
+///  constant multiple of another, bit pattern for bit pattern with the sign of a zero included,
+///  are not stored), AoS packs per table shape, LDS staging.
 //------------------------------------------------------------------------------
 #ifndef gfhip_tables_hpp
 #define gfhip_tables_hpp
@@ -40,10 +41,12 @@ struct table_layout {
 inline table_layout layout_tables(const item &it, const codegen_options &opt) {
 //  Table compaction.  reduce() folds constants into coefficient tables at graph-build time
 //  (arithmetic.hpp:192-247), so a kernel gathers many tables that are a constant times
-//  another one (45 psi tables, 16 independent).  Where fl(k*parent[c]) == table[c] holds for
-//  EVERY cell (checked here, in the item's precision) the table is not stored: its gather
-//  becomes k*(gather of the parent) — the same bits, one multiply instead of a load, and the
-//  2-D pack of the RK4 kernel shrinks from 360 B to one 128 B line per cell.
+//  another one (45 psi tables, 16 independent).  Where fl(k*parent[c]) has the bit pattern of
+//  table[c] in EVERY cell (checked here, in the item's precision; the sign of a zero included:
+//  k*(+0) is -0 for a negative k, and 1/g, atan2 and odd powers tell the two apart; a NaN cell
+//  never matches) the table is not stored: its gather becomes k*(gather of the parent) — the
+//  same bits, one multiply instead of a load, and the 2-D pack of the RK4 kernel shrinks from
+//  360 B to one 128 B line per cell.
     table_layout layout;
     const bool f64 = it.dtype == GFIR_F64;
     const size_t esize = it.element_size();
@@ -86,13 +89,17 @@ inline table_layout layout_tables(const item &it, const codegen_options &opt) {
                 const double p = std::nearbyint(k0*q);
                 if (p != 0.0 && std::fabs(p/q - k0) <= 1.0E-12*std::fabs(k0)) candidates.push_back(p/q);
             }
+//  (equal and of equal sign: the same bit pattern for everything but a NaN, which equals nothing)
+            auto same_bits = [] (const auto product, const auto cell) -> bool {
+                return product == cell && std::signbit(product) == std::signbit(cell);
+            };
             for (const double k : candidates) {
                 bool exact = true;
                 for (size_t c = 0; c < from.data.size() && exact; c++) {
                     if (f64) {
-                        exact = k*from.data[c] == to.data[c];
+                        exact = same_bits(k*from.data[c], to.data[c]);
                     } else {
-                        exact = static_cast<float> (k)*static_cast<float> (from.data[c]) == static_cast<float> (to.data[c]) &&
+                        exact = same_bits(static_cast<float> (k)*static_cast<float> (from.data[c]), static_cast<float> (to.data[c])) &&
                                 static_cast<double> (static_cast<float> (k)) == k;
                     }
                 }

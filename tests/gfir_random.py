@@ -17,8 +17,9 @@ NONE = 0xFFFFFFFF
 
 
 class Builder:
-    def __init__(self, rng, dtype, num_inputs):
+    def __init__(self, rng, dtype, num_inputs, plant_zeros=False):
         self.rng = rng
+        self.plant_zeros = plant_zeros  # some tables get a cell of +0 or -0 (off: the items of the seeds in use stay as they are)
         self.dtype = dtype
         self.real = np.float64 if dtype == "f64" else np.float32
         self.code = []
@@ -65,13 +66,20 @@ class Builder:
         return self.emit(DIV, v, d, bound=0.5)
 
     def table(self, rows, cols):
-        """A new table, or an exact power-of-two multiple of an earlier one of the same shape."""
+        """A new table, or an exact multiple of an earlier one of the same shape.  With `plant_zeros` a new table may
+        get a zero cell of either sign, and a zero cell of a multiple a sign of its own: with the product's sign the
+        lowering may drop the table, with the other one it must store it."""
         same = [t for t in self.tables if t.shape == (rows, cols)]
-        if same and self.rng.random() < 0.4:
+        multiple = bool(same) and self.rng.random() < 0.4
+        if multiple:
             data = same[int(self.rng.integers(0, len(same)))]*float(self.rng.choice([0.5, 2.0, -4.0, 3.0]))
             data = data.astype(self.real).astype(np.float64)
         else:
             data = self.rng.uniform(-1.0, 1.0, (rows, cols)).astype(self.real).astype(np.float64)
+        if self.plant_zeros and self.rng.random() < 0.3:
+            cells = np.flatnonzero(data.ravel() == 0.0) if multiple else np.arange(data.size)
+            if cells.size:
+                data.ravel()[cells[int(self.rng.integers(0, cells.size))]] = self.rng.choice([0.0, -0.0])
         self.tables.append(data)
         return len(self.tables) - 1
 
@@ -130,10 +138,10 @@ class Builder:
         return v
 
 
-def random_item(seed, dtype="f64", num_inputs=6, num_nodes=400, num_outputs=3, num_setters=3, name="fuzz"):
+def random_item(seed, dtype="f64", num_inputs=6, num_nodes=400, num_outputs=3, num_setters=3, name="fuzz", plant_zeros=False):
     """Returns (GFIR bytes, number of instruction records)."""
     rng = np.random.default_rng(seed)
-    b = Builder(rng, dtype, num_inputs)
+    b = Builder(rng, dtype, num_inputs, plant_zeros)
     while len(b.code) < num_nodes:
         b.grow()
     tail = b.values[-max(32, num_outputs + num_setters):]

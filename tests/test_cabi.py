@@ -108,7 +108,8 @@ def test_malformed_items_are_rejected(lib):
 
 
 def test_table_compaction_is_exact(monkeypatch):
-    """Every table the lowering derives as k*parent must equal the exported table bit for bit."""
+    """Every table the lowering derives as k*parent must equal the exported table bit for bit (bit patterns are
+    compared: under == a zero of the wrong sign would pass)."""
     import struct
     from graph_framework_amd import generate_source
     path = os.path.join(WORKLOADS, "solver_kernel_f64.gfir")
@@ -131,7 +132,7 @@ def test_table_compaction_is_exact(monkeypatch):
     assert len(derived) > 100
     for _group, child, factor, parent in derived:
         k = float.fromhex(factor)
-        np.testing.assert_array_equal(k*tables[int(parent)], tables[int(child)])
+        np.testing.assert_array_equal((k*tables[int(parent)]).view(np.uint64), tables[int(child)].view(np.uint64))
 #  the assembly body multiplies the same pairs (its annotations carry the factor's bits)
 #  (table numbers are those of the piece the kernel is lowered from)
     from graph_framework_amd.backend import export_pieces
@@ -142,7 +143,8 @@ def test_table_compaction_is_exact(monkeypatch):
     assert len(multiplied) > 100
     for child, parent, factor_bits in multiplied:
         k = struct.unpack("<d", struct.pack("<Q", int(factor_bits)))[0]
-        np.testing.assert_array_equal(k*piece_tables[int(parent)], piece_tables[int(child)])
+        product, cells = k*np.asarray(piece_tables[int(parent)], dtype=np.float64), np.asarray(piece_tables[int(child)], dtype=np.float64)
+        np.testing.assert_array_equal(product.view(np.uint64), cells.view(np.uint64))
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
