@@ -26,7 +26,7 @@ class KernelInfo(ctypes.Structure):
                 ("lds_bytes", ctypes.c_uint32), ("scratch_bytes", ctypes.c_uint32),
                 ("block_size", ctypes.c_uint32), ("grid_size", ctypes.c_uint32),
                 ("from_cache", ctypes.c_uint32), ("segments", ctypes.c_uint32),
-                ("converge_batch", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("converge_batch", ctypes.c_uint32), ("level", ctypes.c_uint32),
                 ("source_hash", ctypes.c_uint64),
                 ("name", ctypes.c_char*64)]
 
@@ -41,6 +41,7 @@ SYMBOLS = [
     ("gfhip_destroy_context", None, [_P]),
     ("gfhip_last_error", ctypes.c_char_p, [_P]),
     ("gfhip_add_kernel", _P, [_P, _P, _S, _S]),
+    ("gfhip_add_kernel_at", _P, [_P, _P, _S, _S, _U32]),
     ("gfhip_compile", _I, [_P]),
     ("gfhip_create_kernel_call", _I, [_P, _P, _P, _P, _P]),
     ("gfhip_run", _I, [_P, _U32]),
@@ -65,6 +66,9 @@ SYMBOLS = [
     ("gfhip_generate_source", _P, [_P, _S, ctypes.POINTER(_U64)]),
     ("gfhip_generate_piece_source", _I, [_P, _S, _U32, ctypes.POINTER(_P), ctypes.POINTER(_U64)]),
     ("gfhip_export_piece", _I, [_P, _S, _U32, ctypes.POINTER(_P), ctypes.POINTER(_S)]),
+    ("gfhip_generate_source_at", _P, [_P, _S, ctypes.POINTER(_U64), _U32]),
+    ("gfhip_generate_piece_source_at", _I, [_P, _S, _U32, ctypes.POINTER(_P), ctypes.POINTER(_U64), _U32]),
+    ("gfhip_export_piece_at", _I, [_P, _S, _U32, ctypes.POINTER(_P), ctypes.POINTER(_S), _U32]),
     ("gfhip_free_string", None, [_P]),
     ("gfhip_cli_distribution", None, [_U64, _S, _P, _P, _P]),
     ("gfhip_enable_timing", _I, [_P, _I]),

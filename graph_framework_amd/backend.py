@@ -63,12 +63,13 @@ class Context:
         if status:
             raise GfHipError(self.lib.gfhip_last_error(self.handle).decode())
 
-    def add_kernel(self, gfir, num_rays):
-        """jit::context::add_kernel (jit.hpp:118-194) for a serialized work item."""
+    def add_kernel(self, gfir, num_rays, level=0):
+        """jit::context::add_kernel (jit.hpp:118-194) for a serialized work item, at lowering level
+        `level` (include/gf_hip.h, gfhip_add_kernel_at)."""
         if not isinstance(gfir, (bytes, bytearray)):
             with open(gfir, "rb") as f:
                 gfir = f.read()
-        handle = self.lib.gfhip_add_kernel(self.handle, gfir, len(gfir), int(num_rays))
+        handle = self.lib.gfhip_add_kernel_at(self.handle, gfir, len(gfir), int(num_rays), int(level))
         if not handle:
             raise GfHipError(self.lib.gfhip_last_error(self.handle).decode())
         kernel = Kernel(self, handle, int(num_rays))
@@ -244,14 +245,14 @@ class Kernel:
         return ms.value, launches.value
 
 
-def generate_source(gfir):
+def generate_source(gfir, level=0):
     """HIP source and cache hash of a serialized work item (no device needed)."""
     lib = _lib.load()
     if not isinstance(gfir, (bytes, bytearray)):
         with open(gfir, "rb") as f:
             gfir = f.read()
     source_hash = ctypes.c_uint64()
-    text = lib.gfhip_generate_source(gfir, len(gfir), ctypes.byref(source_hash))
+    text = lib.gfhip_generate_source_at(gfir, len(gfir), ctypes.byref(source_hash), int(level))
     if not text:
         raise GfHipError(lib.gfhip_last_error(None).decode())
     source = ctypes.string_at(text).decode()
@@ -259,7 +260,7 @@ def generate_source(gfir):
     return source, source_hash.value
 
 
-def generate_piece_sources(gfir):
+def generate_piece_sources(gfir, level=0):
     """[(HIP source, cache hash)] of the kernels an item runs as: one for most items, one per
     segment for items the lowering cuts into segments (csrc/segments.hpp)."""
     lib = _lib.load()
@@ -269,7 +270,7 @@ def generate_piece_sources(gfir):
     pieces = []
     while True:
         text, source_hash = ctypes.c_void_p(), ctypes.c_uint64()
-        if lib.gfhip_generate_piece_source(gfir, len(gfir), len(pieces), ctypes.byref(text), ctypes.byref(source_hash)):
+        if lib.gfhip_generate_piece_source_at(gfir, len(gfir), len(pieces), ctypes.byref(text), ctypes.byref(source_hash), int(level)):
             raise GfHipError(lib.gfhip_last_error(None).decode())
         if not text:
             return pieces
@@ -277,7 +278,7 @@ def generate_piece_sources(gfir):
         lib.gfhip_free_string(text)
 
 
-def export_pieces(gfir):
+def export_pieces(gfir, level=0):
     """The segments of an item as data (no device): a list of dicts with the piece as GFIR bytes
     and what its symbols and outputs are (include/gf_hip.h, gfhip_export_piece); [] for an item
     that runs as one kernel."""
@@ -289,7 +290,7 @@ def export_pieces(gfir):
     pieces = []
     while True:
         block, size = ctypes.c_void_p(), ctypes.c_size_t()
-        if lib.gfhip_export_piece(gfir, len(gfir), len(pieces), ctypes.byref(block), ctypes.byref(size)):
+        if lib.gfhip_export_piece_at(gfir, len(gfir), len(pieces), ctypes.byref(block), ctypes.byref(size), int(level)):
             raise GfHipError(lib.gfhip_last_error(None).decode())
         if not block:
             return pieces

@@ -40,6 +40,9 @@ def compile_source(source, source_hash, force=False):
     return stem + ".hsaco"
 
 
+LEVELS = (0, 1)         # lowering levels whose code objects are pre-built (include/gf_hip.h, gfhip_add_kernel_at)
+
+
 def prebuild_kernel(gfir_path, force=False):
     """Lower one workload item and compile it — every segment of it, for an item the lowering cuts
     into segments — to gfx950 code objects in the kernel cache."""
@@ -79,6 +82,14 @@ def prebuild_workloads(force=False):
     from . import backend
     paths = sorted(glob.glob(os.path.join(_lib.WORKLOAD_DIR, "*.gfir")))
     texts = [piece for path in paths for piece in backend.generate_piece_sources(path)] + variant_sources()
+#  Level 1 of every workload whose text it changes (the items whose pass is the assembly statement): same hash, same text otherwise.
+    known = {source_hash for _, source_hash in texts}
+    for level in LEVELS[1:]:
+        for path in paths:
+            for piece in backend.generate_piece_sources(path, level):
+                if piece[1] not in known:
+                    known.add(piece[1])
+                    texts.append(piece)
     workers = max(1, min(8, (os.cpu_count() or 4)))
     with ThreadPoolExecutor(max_workers=workers) as pool:
         built = list(pool.map(lambda piece: compile_source(piece[0], piece[1], force), texts))

@@ -27,6 +27,16 @@
 ///  kernel, lanes outside the window are redone by the redo launch).
 ///
 ///  Items it does not take (complex, SAFE_MATH, fp32, ops without a sequence here) keep the compiled body.
+///
+///  Lowering level 1 (options.hpp `level`, asked for by the caller) writes fewer instructions for the same stored bits:
+///    * the statement is written from the piece merged once more (merge.hpp, level 1: commutative twins, equal square
+///      roots and pow records, mul(-1.0, x) numbered as neg(x));
+///    * a mul by the constant -1.0, and a gather of a table that is -1.0 times its parent, write nothing where every
+///      use can read the value under a VOP3 `neg` modifier (operands of add, sub, mul, fma, numerators of quotients);
+///    * a table value -k*p wanted by such a use while k*p of the same cell sits in a register is that register under `neg`.
+///  Each fold gives the same bits for every operand that is not a NaN; a lane with a NaN anywhere stores a NaN (no sequence
+///  here turns one into a number, and an index quotient that is one fails the finite check), and every lane that stores
+///  a non-finite value is computed again by the redo kernel, which is the same kernel at both levels.  DESIGN.md section 3.
 //------------------------------------------------------------------------------
 #ifndef gfhip_asm_body_hpp
 #define gfhip_asm_body_hpp
@@ -57,6 +67,11 @@ struct asm_body_text {
     std::string statement;              ///< the asm volatile(...) statement
     uint32_t slots = 0;                 ///< LDS slots (block_size elements each) of values sent out of the registers
     size_t vector = 0, scalar = 0, lds_reads = 0, lds_writes = 0, loads = 0, waits = 0;
+//  Level 1 (options.hpp): records that became a `neg` modifier on their uses, and those that some use kept as an instruction.
+    size_t signs_folded = 0, signs_kept = 0;            ///< mul records with the constant -1.0
+    size_t tables_folded = 0, tables_kept = 0;          ///< gathers of a table derived from its parent by the factor -1.0
+    size_t twins_folded = 0, twins_made = 0;            ///< uses of -k*p read from a register that holds k*p; products of a table that has
+                                                        ///< such a twin made all the same (the twin was not in a register, or the use takes no modifier)
 };
 
 class asm_body_writer {
@@ -94,6 +109,8 @@ class asm_body_writer {
     };
     std::vector<value> values;
     std::vector<int64_t> alias;                         ///< node -> value it stands for
+    std::vector<bool> negated;                          ///< ... with the opposite sign (level 1: every use flips its `neg` modifier)
+    std::vector<bool> folded;                           ///< a mul by -1.0 that is only such a name: no instruction
     std::vector<std::vector<int64_t>> used_at;          ///< position -> values read there
     std::vector<int64_t> owner;                         ///< pair -> value, -1 free, -2 held by the sequence being written
     std::vector<int> free_slots;
@@ -230,9 +247,35 @@ class asm_body_writer {
 
 //  Who reads what where.  A gather node stands for the table value of its group's cell; a derived table's value
 //  reads its parent's at each of its own uses (it may have to be made again after it lost its register).
+//
+//  Level 1: a mul by the constant -1.0, and a gather of a table that is -1.0 times its parent, write no instruction where
+//  every use can take the value under a `neg` modifier instead: operands of add, sub, mul and fma and numerators of
+//  quotients.  A record that is stored, indexes a table, is a denominator, a root's argument (the window check reads its
+//  register) or the base of a power stays the multiplication it is.
+    std::vector<bool> needs_register() const {
+        std::vector<bool> needed(n, false);
+        for (size_t i = 0; i < n; i++) {
+            const gfir_instruction &c = it.code[i];
+            if (it.is_merged(i)) continue;
+            switch (c.op) {
+                case GFIR_GATHER2: needed[c.b] = true; needed[c.a] = true; break;
+                case GFIR_GATHER1: case GFIR_POWI: case GFIR_SQRT: case GFIR_POW: needed[c.a] = true; break;
+                case GFIR_DIV: needed[c.b] = true; break;
+                default: break;
+            }
+        }
+        for (auto &st : it.setters) needed[st.value] = true;
+        for (auto o : it.outputs) needed[o] = true;
+        return needed;
+    }
+    static bool is_minus_one(const gfir_instruction &c) { return c.op == GFIR_CONST && c.imm[0] == -1.0 && c.imm[1] == 0.0; }
+
     void analyse() {
         values.assign(2*n, value());
         alias.assign(n, -1);
+        negated.assign(n, false);
+        folded.assign(n, false);
+        const std::vector<bool> needed = opt.level >= 1 ? needs_register() : std::vector<bool> ();
         used_at.assign(n, std::vector<int64_t> ());
         node_group.assign(n, -1);
         for (size_t i = 0; i < n; i++) {
@@ -250,13 +293,33 @@ class asm_body_writer {
                     found = group_of_key.insert({key, static_cast<int> (groups.size()) - 1}).first;
                 }
                 node_group[i] = found->second;
+                if (opt.level >= 1 && !it.is_merged(i) && parent[c.aux] >= 0 && factor[c.aux] == -1.0) {
+                    if (!needed[i]) {
+                        alias[i] = cell_value(found->second, static_cast<uint32_t> (parent[c.aux]));
+                        negated[i] = true;
+                        result.tables_folded++;
+                        continue;
+                    }
+                    result.tables_kept++;
+                }
                 alias[i] = cell_value(found->second, c.aux);
+            } else if (opt.level >= 1 && c.op == GFIR_MUL && !it.is_merged(i) && is_minus_one(it.code[c.a]) != is_minus_one(it.code[c.b])) {
+                const uint32_t x = is_minus_one(it.code[c.a]) ? c.b : c.a;
+                if (it.code[x].op == GFIR_CONST) continue;
+                if (needed[i]) {
+                    result.signs_kept++;
+                    continue;
+                }
+                alias[i] = alias[x];
+                negated[i] = !negated[x];
+                folded[i] = true;
+                result.signs_folded++;
             }
         }
         std::vector<bool> group_seen(groups.size(), false);
         for (size_t i = 0; i < n; i++) {
             const gfir_instruction &c = it.code[i];
-            if (c.op == GFIR_CONST || c.op == GFIR_INPUT || it.is_merged(i)) continue;    // (a merged record reads nothing: merge.hpp)
+            if (c.op == GFIR_CONST || c.op == GFIR_INPUT || it.is_merged(i) || folded[i]) continue;    // (a merged record reads nothing: merge.hpp)
             if (c.op == GFIR_GATHER1 || c.op == GFIR_GATHER2) {
 //  The arguments are read where the group's cell is found: at its first gather.
                 const size_t g = static_cast<size_t> (node_group[i]);
@@ -426,6 +489,7 @@ class asm_body_writer {
                 wait_for(values[static_cast<size_t> (up)]);
                 const int p = need_pair();
                 const std::string scaled = constant_operand(factor[v.table], nullptr);
+                if (twin_of(id, false) >= 0) result.twins_made++;
                 annotate("def " + value_name(id) + " = " + value_name(up) + " * " + std::to_string(bits_of(factor[v.table])));
                 vector_op("v_mul_f64 " + pair_name(p) + ", " + name_of(up) + ", " + scaled);
                 if (!was_pinned) pinned.erase(up);
@@ -516,6 +580,18 @@ class asm_body_writer {
         return true;
     }
 
+//  Level 1: the table value `id` = k*p is not in a register, but -k*p of the same cell and parent is: that value.
+    int64_t twin_of(const int64_t id, const bool resident) const {
+        const value &v = values[static_cast<size_t> (id)];
+        if (opt.level < 1 || !v.loadable || parent[v.table] < 0) return -1;
+        for (auto &kv : groups[static_cast<size_t> (v.group)].cells) {
+            const value &w = values[static_cast<size_t> (kv.second)];
+            if (kv.second == id || parent[w.table] != parent[v.table] || factor[w.table] != -factor[v.table]) continue;
+            if (!resident || (w.reg >= 0 && !in_flight(w))) return kv.second;
+        }
+        return -1;
+    }
+
     std::string name_of(const int64_t id) const {
         const value &v = values[static_cast<size_t> (id)];
         return v.operand.empty() ? pair_name(v.reg) : v.operand;
@@ -604,25 +680,39 @@ class asm_body_writer {
     };
 //  The texts of the operands `nodes` of one instruction (values brought into registers and waited for, constants
 //  resolved); `negate[k]` flips the sign of operand k (a modifier for registers, the negated constant otherwise).
-    operands resolve(const std::vector<uint32_t> &nodes, const std::vector<bool> &negate = std::vector<bool> ()) {
+//  `modifiers`: every operand may be read under `neg` (level 1: a table value -k*p is then read from the register of k*p).
+    operands resolve(const std::vector<uint32_t> &nodes, const std::vector<bool> &negate = std::vector<bool> (), const bool modifiers = false) {
         operands out;
-        for (const uint32_t o : nodes) {
-            if (it.code[o].op != GFIR_CONST) pinned.insert(alias[o]);
+        std::vector<int64_t> read(nodes.size(), -1);
+        std::vector<bool> flipped(nodes.size(), false);
+        for (size_t k = 0; k < nodes.size(); k++) {
+            if (it.code[nodes[k]].op == GFIR_CONST) continue;
+            read[k] = alias[nodes[k]];
+            const int64_t twin = modifiers && values[static_cast<size_t> (read[k])].reg < 0 ? twin_of(read[k], true) : -1;
+            if (twin >= 0) {
+                const value &v = values[static_cast<size_t> (read[k])];
+                line("; twin " + value_name(read[k]) + " = " + value_name(cell_value(v.group, static_cast<uint32_t> (parent[v.table]))) + " * " +
+                     std::to_string(bits_of(factor[values[static_cast<size_t> (read[k])].table])));
+                read[k] = twin;
+                flipped[k] = true;
+                result.twins_folded++;
+            }
+            pinned.insert(read[k]);
         }
-        for (const uint32_t o : nodes) {
-            if (it.code[o].op != GFIR_CONST) fetch(alias[o]);
+        for (const int64_t id : read) {
+            if (id >= 0) fetch(id);
         }
-        for (const uint32_t o : nodes) {
-            if (it.code[o].op != GFIR_CONST) wait_for(values[static_cast<size_t> (alias[o])]);
+        for (const int64_t id : read) {
+            if (id >= 0) wait_for(values[static_cast<size_t> (id)]);
         }
         int taken = -1;
         for (size_t k = 0; k < nodes.size(); k++) {
             const uint32_t o = nodes[k];
-            const bool minus = k < negate.size() && negate[k];
+            const bool minus = (k < negate.size() && negate[k]) != ((negated[o] != flipped[k]) && it.code[o].op != GFIR_CONST);
             if (it.code[o].op == GFIR_CONST) {
                 out.text.push_back(constant_operand(minus ? -it.code[o].imm[0] : it.code[o].imm[0], &taken, &out.spare));
             } else {
-                out.text.push_back((minus ? "-" : "") + name_of(alias[o]));
+                out.text.push_back((minus ? "-" : "") + name_of(read[k]));
             }
         }
         return out;
@@ -799,6 +889,10 @@ class asm_body_writer {
             line("; alias r" + std::to_string(i) + " = r" + std::to_string(it.merged_into[i]));
             return;
         }
+        if (folded[i]) {
+            line("; alias r" + std::to_string(i) + " = " + (negated[i] ? "-" : "") + value_name(alias[i]));
+            return;
+        }
         look_ahead();
         std::vector<int64_t> read = used_at[i];
         switch (c.op) {
@@ -811,13 +905,13 @@ class asm_body_writer {
             case GFIR_GATHER1:
             case GFIR_GATHER2:
                 if (groups[static_cast<size_t> (node_group[i])].offset_pair == -1) find_cell(i);
-                line("; alias r" + std::to_string(i) + " = " + value_name(alias[i]));
+                line("; alias r" + std::to_string(i) + " = " + (negated[i] ? "-" : "") + value_name(alias[i]));
                 break;
             case GFIR_ADD:
             case GFIR_SUB:
             case GFIR_MUL:
             case GFIR_FMA: {
-                operands x = c.op == GFIR_FMA ? resolve({c.a, c.b, c.c}) : resolve({c.a, c.b}, {false, c.op == GFIR_SUB});
+                operands x = c.op == GFIR_FMA ? resolve({c.a, c.b, c.c}, {}, true) : resolve({c.a, c.b}, {false, c.op == GFIR_SUB}, true);
                 retire(read);
                 read.clear();
                 const int p = need_pair();
@@ -1050,6 +1144,9 @@ class asm_body_writer {
 ///  lifted; with two waves per SIMD a lane has 40 slots at most, the RK4 item needs 19 with its best order and 65
 ///  with the order schedule_for_pressure picks for the compiler.
 //------------------------------------------------------------------------------
+///  The search does not depend on the lowering level (options.hpp): the kernel text around the statement follows the order
+///  (the inputs are loaded in the order of their records), and the level is to change nothing but the statement.  The
+///  candidates' statements are therefore the level-0 ones, and one remembered seed serves both levels.
 ///  With options.merge the statement of a candidate is written for its merged form (merge.hpp: the representative of equal
 ///  records is the earliest in the candidate's order); the order comes back unmerged.
 ///  `directories`: where the seed of the chosen order is remembered (`<hash of item and knobs>.order`, next to the code
@@ -1085,7 +1182,9 @@ inline item schedule_for_assembly(const item &in, const codegen_options &opt, co
     for (uint32_t seed = 0; seed < std::max(1u, tries); seed++) {
         item candidate = reorder(in, list_schedule(in, seed));
         const item merged = opt.merge ? merge_records(candidate) : item();
-        asm_body_writer writer(opt.merge ? merged : candidate, opt, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column,
+        codegen_options plain = opt;
+        plain.level = 0;
+        asm_body_writer writer(opt.merge ? merged : candidate, plain, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column,
                                opt.block_size, 1u << 20);
         const asm_body_text text = writer.write();
         if (!text.ok) continue;
@@ -1126,17 +1225,40 @@ inline uint32_t assembly_slot_limit(const size_t lds_used, const codegen_options
 }
 
 ///  The statement of `piece` (in emission order, merged) within the LDS a workgroup has; `ok` is false if it cannot be written.
+///  At level 1 it is written from the piece merged once more (merge.hpp, level 1): the records keep their numbers, and
+///  nothing but the statement sees that form.  A piece takes the level-1 statement only where it takes the level-0 one
+///  (and the other way round), so that the level decides about nothing but the statement's text.
 inline asm_body_text assembly_statement(const item &piece, const codegen_options &opt) {
     const table_layout layout = layout_tables(piece, opt);
-    asm_body_writer writer(piece, opt, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column, opt.block_size,
-                           assembly_slot_limit(layout.lds_used, opt, piece.element_size()));
-    const asm_body_text text = writer.write();
-    if (std::getenv("GFHIP_ASM_REPORT")) {
-        std::fprintf(stderr, "assembly body of %s: %s; %zu vector, %zu scalar, %zu table loads, %zu LDS reads, %zu LDS writes, %zu waits, %u slots\n",
-                     piece.name.c_str(), text.ok ? "ok" : text.why.c_str(), text.vector, text.scalar, text.loads,
+    const uint32_t slot_limit = assembly_slot_limit(layout.lds_used, opt, piece.element_size());
+    auto write = [&] (const item &form, const codegen_options &options) {
+        asm_body_writer writer(form, options, layout.packs, layout.parent, layout.factor, layout.table_pack, layout.table_column, options.block_size,
+                               slot_limit);
+        return writer.write();
+    };
+    auto report = [&] (const asm_body_text &text, const char *what) {
+        if (!std::getenv("GFHIP_ASM_REPORT")) return;
+        std::fprintf(stderr, "assembly body of %s%s: %s; %zu vector, %zu scalar, %zu table loads, %zu LDS reads, %zu LDS writes, %zu waits, %u slots\n",
+                     piece.name.c_str(), what, text.ok ? "ok" : text.why.c_str(), text.vector, text.scalar, text.loads,
                      text.lds_reads, text.lds_writes, text.waits, text.slots);
+    };
+    codegen_options plain = opt;
+    plain.level = 0;
+    const asm_body_text text = write(piece, plain);
+    report(text, "");
+    if (opt.level < 1 || !text.ok) return text;
+    merge_report merges;
+    const item again = opt.merge ? merge_records(piece, &merges, opt.level) : item();
+    const asm_body_text folded = write(opt.merge ? again : piece, opt);
+    report(folded, " (level 1)");
+    if (std::getenv("GFHIP_ASM_REPORT")) {
+        if (opt.merge) merges.print(stderr, piece.name + " (level 1)");
+        std::fprintf(stderr, "level 1 folds of %s: mul by -1.0: %zu folded, %zu kept; gathers of a table derived by -1.0: %zu folded, %zu kept; "
+                             "-k*p read from the register of k*p: %zu times, multiplied all the same: %zu times; %zu vector instructions fewer\n",
+                     piece.name.c_str(), folded.signs_folded, folded.signs_kept, folded.tables_folded, folded.tables_kept, folded.twins_folded,
+                     folded.twins_made, text.vector - folded.vector);
     }
-    return text;
+    return folded.ok ? folded : text;
 }
 
 }  // namespace gfhip

@@ -186,6 +186,7 @@ struct gfhip_kernel {
     device_ptr<unsigned char> flagged;             // per ray: a segment before the last found it outside the window
     device_ptr<unsigned int> redo_list, redo_count;
     size_t num_rays = 0;
+    uint32_t level = 0;                            // lowering level the item was planned at (options.hpp)
     std::vector<device_ptr<>> undo;                // per setter: the target's values at the beginning of the last batch
 //  gfhip_run_max called in a row (the reference's converge_item::run, workflow.hpp:179-205, through hip_context's
 //  create_max_call): passes of the last `<name>_batch` launch that ran ahead of the caller, their maxes waiting here.
@@ -305,20 +306,28 @@ static std::vector<std::string> cache_directories() {
     return directories;
 }
 
-//  Parse an item and plan its lowering (plan.hpp) under the options of the environment, read here once per entry point.
-static bool parse_and_plan(const void *gfir, const size_t bytes, gfhip::item &it, gfhip::item_plan &plan, std::string &error) {
+//  Parse an item and plan its lowering (plan.hpp) at the level the caller asks for, under the options of the environment
+//  (GFHIP_LEVEL among them: it overrides the caller), read here once per entry point.
+static bool parse_and_plan(const void *gfir, const size_t bytes, const uint32_t level, gfhip::item &it, gfhip::item_plan &plan,
+                           std::string &error, uint32_t *planned_level = nullptr) {
     if (!it.parse(gfir, bytes, error)) return false;
-    plan = gfhip::plan_item(it, gfhip::codegen_options::from_environment(), cache_directories());
+    const gfhip::codegen_options options = gfhip::codegen_options::from_environment(level);
+    if (planned_level) *planned_level = options.level;
+    plan = gfhip::plan_item(it, options, cache_directories());
     return true;
 }
 
 extern "C" gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, size_t bytes, size_t num_rays) {
+    return gfhip_add_kernel_at(ctx, gfir, bytes, num_rays, 0);
+}
+
+extern "C" gfhip_kernel *gfhip_add_kernel_at(gfhip_context *ctx, const void *gfir, size_t bytes, size_t num_rays, uint32_t level) {
     if (!ctx) return nullptr;
     std::unique_ptr<gfhip_kernel> k(new gfhip_kernel);
     k->ctx = ctx;
     k->num_rays = num_rays;
     gfhip::item_plan plan;
-    if (!parse_and_plan(gfir, bytes, k->item, plan, ctx->error)) {
+    if (!parse_and_plan(gfir, bytes, level, k->item, plan, ctx->error, &k->level)) {
         return nullptr;
     }
     k->whole.low = std::move(plan.whole);
@@ -333,12 +342,16 @@ extern "C" gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, 
 }
 
 extern "C" int gfhip_export_piece(const void *gfir, size_t bytes, uint32_t index, void **piece, size_t *piece_bytes) {
+    return gfhip_export_piece_at(gfir, bytes, index, piece, piece_bytes, 0);
+}
+
+extern "C" int gfhip_export_piece_at(const void *gfir, size_t bytes, uint32_t index, void **piece, size_t *piece_bytes, uint32_t level) {
     gfhip::item it;
     gfhip::item_plan planned;
     if (!piece || !piece_bytes) return 1;
     *piece = nullptr;
     *piece_bytes = 0;
-    if (!parse_and_plan(gfir, bytes, it, planned, creation_error)) return 1;
+    if (!parse_and_plan(gfir, bytes, level, it, planned, creation_error)) return 1;
     if (index >= planned.pieces.size()) return 0;
     const gfhip::segment &plan = planned.pieces[index].plan;
     std::vector<int32_t> head = {static_cast<int32_t> (plan.piece.symbols.size()), static_cast<int32_t> (plan.piece.outputs.size()),
@@ -356,11 +369,16 @@ extern "C" int gfhip_export_piece(const void *gfir, size_t bytes, uint32_t index
 }
 
 extern "C" int gfhip_generate_piece_source(const void *gfir, size_t bytes, uint32_t index, char **source, uint64_t *source_hash) {
+    return gfhip_generate_piece_source_at(gfir, bytes, index, source, source_hash, 0);
+}
+
+extern "C" int gfhip_generate_piece_source_at(const void *gfir, size_t bytes, uint32_t index, char **source, uint64_t *source_hash,
+                                              uint32_t level) {
     gfhip::item it;
     gfhip::item_plan plan;
     if (!source) return 1;
     *source = nullptr;
-    if (!parse_and_plan(gfir, bytes, it, plan, creation_error)) return 1;
+    if (!parse_and_plan(gfir, bytes, level, it, plan, creation_error)) return 1;
     const gfhip::lowered *low = nullptr;
     if (plan.pieces.empty()) {
         if (index == 0) low = &plan.whole;
@@ -377,9 +395,13 @@ extern "C" int gfhip_generate_piece_source(const void *gfir, size_t bytes, uint3
 }
 
 extern "C" char *gfhip_generate_source(const void *gfir, size_t bytes, uint64_t *source_hash) {
+    return gfhip_generate_source_at(gfir, bytes, source_hash, 0);
+}
+
+extern "C" char *gfhip_generate_source_at(const void *gfir, size_t bytes, uint64_t *source_hash, uint32_t level) {
     gfhip::item it;
     gfhip::item_plan plan;
-    if (!parse_and_plan(gfir, bytes, it, plan, creation_error)) return nullptr;
+    if (!parse_and_plan(gfir, bytes, level, it, plan, creation_error)) return nullptr;
 //  An item in pieces: the texts of its pieces one after the other (each is a translation unit of its
 //  own: gfhip_generate_piece_source hands them out one by one).
     std::string text = plan.whole.source;
@@ -1381,6 +1403,7 @@ extern "C" int gfhip_kernel_get_info(const gfhip_kernel *k, struct gfhip_kernel_
     info->lds_bytes = static_cast<uint32_t> (whole.lds_static + lds);
     info->segments = static_cast<uint32_t> (k->pieces.size());          // segments the item runs as (0: one kernel)
     info->converge_batch = whole.batch_function ? whole.low.batch : 0;
+    info->level = k->level;
     info->scratch_bytes = static_cast<uint32_t> (whole.scratch);
     info->block_size = whole.low.block_size;
     info->grid_size = whole.grid;

@@ -70,12 +70,18 @@ struct codegen_options {
                                         ///< Measured (profiles/r03_asm_sweep.jsonl): 0/0 2.19 ms, 24/6 1.88, 48/12 1.85, 96/24 1.82; pool from v48: 1.83
     bool merge = true;                  ///< records that hold the same bits are merged before anything else sees the item (merge.hpp;
                                         ///< GFHIP_MERGE=0: the item as it arrives)
+    uint32_t level = 0;                 ///< lowering level, asked for by the caller (gfhip_add_kernel_at; GFHIP_LEVEL overrides it): 0 = the text the
+                                        ///< library has always written; 1 = the assembly statement also folds what only the redo launch makes exact —
+                                        ///< mul by -1.0 and tables derived by -1.0 as `neg` modifiers, commutative twins, equal sqrt and pow records
+                                        ///< (merge.hpp, asm_body.hpp).  Nothing outside the statement depends on it
     size_t handover_bytes = 128u << 20; ///< the hand-over buffers of a segmented item hold one chunk of rays and at most this many
                                         ///< bytes, so that they stay in the 256 MB Infinity Cache (GFHIP_HANDOVER_BYTES)
 
 //  Environment overrides (they change the generated text, hence the cache key): for the entry points of gf_hip.cpp.
-    static codegen_options from_environment() {
+    static codegen_options from_environment(const uint32_t level = 0) {
         codegen_options o;
+        o.level = level;
+        if (const char *e = std::getenv("GFHIP_LEVEL")) o.level = std::atoi(e) > 0 ? 1 : 0;
         if (const char *e = std::getenv("GFHIP_DIVISION")) {
             const std::string mode(e);
             o.division = mode == "ieee" ? division_mode::ieee : mode == "checked" ? division_mode::checked

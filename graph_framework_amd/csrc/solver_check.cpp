@@ -34,6 +34,7 @@ int main(int argc, char **argv) {
     };
     std::printf("newton_iterations %zu\n", solve.newton_iterations);
     print(solve.newton_residual(0));
+    solve.solver_level = 1;
     solve.compile();
     bool holds = true;
     for (size_t i = 0; i < steps; i++) {

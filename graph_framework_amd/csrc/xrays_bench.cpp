@@ -100,6 +100,7 @@ int main(int argc, char **argv) {
             time_init.end_time(i);
 
             time_compile.start_time(i);
+            solve.solver_level = 1;
             solve.compile();
             time_compile.end_time(i);
 

@@ -73,9 +73,10 @@ protected:
 
 public:
     work_item(gfhip_context *ctx, const std::vector<char> &gfir, const std::vector<std::string> &in,
-              const std::vector<std::string> &out, const size_t size, const std::map<std::string, const T *> &init) :
-    context(ctx), kernel(gfhip_add_kernel(ctx, gfir.data(), gfir.size(), size)), inputs(in), outputs(out), initial(init) {
-        if (!kernel) fail("gfhip_add_kernel");
+              const std::vector<std::string> &out, const size_t size, const std::map<std::string, const T *> &init,
+              const uint32_t level = 0) :
+    context(ctx), kernel(gfhip_add_kernel_at(ctx, gfir.data(), gfir.size(), size, level)), inputs(in), outputs(out), initial(init) {
+        if (!kernel) fail("gfhip_add_kernel_at");
     }
     virtual ~work_item() {}
 
@@ -170,8 +171,8 @@ public:
     }
     work_item<T> *add_item(const std::vector<char> &gfir, const std::vector<std::string> &inputs,
                            const std::vector<std::string> &outputs, const size_t size,
-                           const std::map<std::string, const T *> &initial = {}) {
-        items.emplace_back(new work_item<T> (context, gfir, inputs, outputs, size, initial));
+                           const std::map<std::string, const T *> &initial = {}, const uint32_t level = 0) {
+        items.emplace_back(new work_item<T> (context, gfir, inputs, outputs, size, initial, level));
         return items.back().get();
     }
     converge_item<T> *add_converge_item(const std::vector<char> &gfir, const std::vector<std::string> &inputs,
@@ -240,6 +241,7 @@ public:
 ///  Host copies of the ray variables (the reference's variable nodes), input order of the kernels.
     std::map<std::string, std::vector<T>> state;
     size_t newton_iterations = 0;
+    uint32_t solver_level = 0;              ///< lowering level compile() asks for the `solver_kernel` item (gfhip_add_kernel_at)
 
     ray_solver(const std::string &workload_directory, const std::string &workload_prefix, const size_t rays,
                const size_t index = 0) :
@@ -262,7 +264,7 @@ public:
 
 ///  solver_interface::compile (solver.hpp:303-349).
     void compile() {
-        solver_item = work.add_item(read_item(item_path("solver_kernel")), names, {"residual"}, num_rays, initial());
+        solver_item = work.add_item(read_item(item_path("solver_kernel")), names, {"residual"}, num_rays, initial(), solver_level);
         if (gfhip_compile(work.get_context())) solver_item->fail("gfhip_compile");
         solver_item->create_kernel_call();
     }

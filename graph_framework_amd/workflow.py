@@ -14,8 +14,8 @@ from .backend import Context, key_of
 class WorkItem:
     """workflow::work_item (workflow.hpp:22-76)."""
 
-    def __init__(self, context, gfir, inputs, outputs, size, initial=None):
-        self.kernel = context.add_kernel(gfir, size)
+    def __init__(self, context, gfir, inputs, outputs, size, initial=None, level=0):
+        self.kernel = context.add_kernel(gfir, size, level)
         self.inputs = list(inputs)
         self.outputs = list(outputs)
         self.initial = initial
@@ -60,8 +60,8 @@ class Manager:
         self.preitems.append(item)
         return item
 
-    def add_item(self, gfir, inputs, outputs, size, initial=None):
-        item = WorkItem(self.context, gfir, inputs, outputs, size, initial)
+    def add_item(self, gfir, inputs, outputs, size, initial=None, level=0):
+        item = WorkItem(self.context, gfir, inputs, outputs, size, initial, level)
         self.items.append(item)
         return item
 

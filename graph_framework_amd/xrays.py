@@ -58,6 +58,8 @@ class RaySolver:
     (integrator x dispersion relation x equilibrium) whose `loss_kernel_<unknown>` and
     `solver_kernel` items exist as `<workload_prefix><item>_<dtype>.gfir`."""
 
+    solver_level = 0        # lowering level asked for the `solver_kernel` item (include/gf_hip.h, gfhip_add_kernel_at)
+
     def __init__(self, state, dtype="f64", index=0, stream=None, prefix="", items=None, device_state=False,
                  dispersion="cold_plasma", workload_prefix=None):
         """state: dict of host arrays (or scalars) t,w,x,y,z,kx,ky,kz for this shard.
@@ -134,7 +136,7 @@ class RaySolver:
         """solver_interface::compile (solver.hpp:303-349): the `solver_kernel` item."""
         work = self.work
         self.solver = work.add_item(self._item("solver_kernel"), self.keys, [self.residual_key],
-                                    self.num_rays, self._initial())
+                                    self.num_rays, self._initial(), level=self.solver_level)
         work.context.compile()
         self.solver.create_kernel_call()
 
@@ -163,7 +165,8 @@ class RaySolver:
 
 class Rk4ColdPlasmaEfit(RaySolver):
     """solver::rk4<dispersion::cold_plasma<T>> on an EFIT equilibrium (the xrays_bench
-    combination; `dispersion="ordinary_wave"` selects physics_test.cpp:583-618's)."""
+    combination; `dispersion="ordinary_wave"` selects physics_test.cpp:583-618's).  Its step is lowered at level 1."""
+    solver_level = 1
 
 
 class AdaptiveRk4ColdPlasmaEfit(RaySolver):

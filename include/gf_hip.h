@@ -72,6 +72,15 @@ const char *gfhip_last_error(const gfhip_context *ctx);
  * (cuda_context.hpp:713-946, cpu_context.hpp:428-584). */
 gfhip_kernel *gfhip_add_kernel(gfhip_context *ctx, const void *gfir, size_t bytes, size_t num_rays);
 
+/* The same at a lowering level the caller chooses; gfhip_add_kernel is level 0.
+ *   0  the lowering as it has always been;
+ *   1  the assembly statement of a large fp64 item (the RK4 step) also folds what is exact for every operand but a NaN:
+ *      multiplications by -1.0 become sign modifiers, records that differ in operand order and equal square roots are
+ *      computed once.  Lanes that store a NaN are computed again by the unchanged redo kernel, so the stored bits are
+ *      those of level 0.  Items whose pass is compiled have the same text at both levels.
+ * GFHIP_LEVEL=0|1 in the environment overrides `level`; gfhip_kernel_get_info reports the level in force. */
+gfhip_kernel *gfhip_add_kernel_at(gfhip_context *ctx, const void *gfir, size_t bytes, size_t num_rays, uint32_t level);
+
 /* Lower and build every kernel added so far (pre-built code objects are looked
  * up by source hash in the kernel cache directories, otherwise hipRTC).
  * Replaces  void compile(source, names, add_reduction)  (cuda_context.hpp:194-302, jit.hpp:238-244). */
@@ -205,7 +214,7 @@ struct gfhip_kernel_info {
     uint32_t from_cache;            /* 1 if the code object came from the kernel cache */
     uint32_t segments;              /* kernels the item runs as when it was cut into segments, else 0 */
     uint32_t converge_batch;        /* passes per launch of gfhip_converge's loop (`<name>_batch`), 0 or 1: one launch per pass */
-    uint32_t reserved;
+    uint32_t level;                 /* lowering level the kernel was planned at (gfhip_add_kernel_at, GFHIP_LEVEL) */
     uint64_t source_hash;
     char     name[64];
 };
@@ -231,6 +240,10 @@ int gfhip_generate_piece_source(const void *gfir, size_t bytes, uint32_t index, 
  * followed by the piece as a GFIR item (include/gfir.h).  *piece stays NULL past the last piece and
  * for items that run as one kernel. */
 int gfhip_export_piece(const void *gfir, size_t bytes, uint32_t index, void **piece, size_t *piece_bytes);
+/* The three above at a lowering level (gfhip_add_kernel_at); the plain names are level 0. */
+char *gfhip_generate_source_at(const void *gfir, size_t bytes, uint64_t *source_hash, uint32_t level);
+int gfhip_generate_piece_source_at(const void *gfir, size_t bytes, uint32_t index, char **source, uint64_t *source_hash, uint32_t level);
+int gfhip_export_piece_at(const void *gfir, size_t bytes, uint32_t index, void **piece, size_t *piece_bytes, uint32_t level);
 void gfhip_free_string(char *text);
 
 /* Host side, no device: the initial conditions of the xrays command line for one shard, sample
