@@ -2,7 +2,7 @@
 """Secondary measurements (not the driver's contract; bench.py is): the other items of the hot
 path at BASELINE.json's sizes, each with HIP-event kernel time and its HBM-roofline fraction.
 
-    python bench_extra.py korc_f32 | korc_f64 | loss | cli | fused | deposition
+    python bench_extra.py korc_f32 | korc_f64 | loss | cli | fused | deposition | hand_over
 """
 import json
 import os
@@ -331,6 +331,38 @@ def deposition(which="both", rays=100000, records=1000, cells=64):
     return out
 
 
+def hand_over(n=10000000, launches=20):
+    """gfhip_hand_over on the absorption stage's traffic: eight fp64 arrays widened into eight complex ones in ONE
+    launch (pipeline.OnePass does this per record).  Both contexts share a stream, as in the pipeline; the time is
+    between two events around `launches` calls (run it under `rocprofv3 --kernel-trace --stats` for the kernel alone)."""
+    import torch
+    import graph_framework_amd as gfa
+    from graph_framework_amd import _lib
+    from graph_framework_amd.backend import key_of
+    stream_ = torch.cuda.Stream()
+    source, to = gfa.Context(0, stream_.cuda_stream), gfa.Context(0, stream_.cuda_stream)
+    names = ("w", "kx", "ky", "kz", "x", "y", "z", "t")
+    for name in names:
+        source._check(source.lib.gfhip_allocate_buffer(source.handle, key_of(name), n, _lib.GFIR_F64))
+        to._check(to.lib.gfhip_allocate_buffer(to.handle, key_of(name), n, _lib.GFIR_C64))
+    entries = [(name, name) for name in names]
+    to.hand_over(source, entries)
+    to.wait()
+    first, last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    first.record(stream_)
+    for _ in range(launches):
+        to.hand_over(source, entries)
+    last.record(stream_)
+    last.synchronize()
+    ms = first.elapsed_time(last)/launches
+    achieved = 24.0*n*len(names)/(ms*1.0e-3)/1.0e9
+    source.close()
+    to.close()
+    return {"workload": "hand-over, %d fp64 arrays of %d elements widened to complex in one launch" % (len(names), n),
+            "kernel": "hand_over_kernel", "ms_per_launch": ms, "read_MB_per_array": 8.0e-6*n, "written_MB_per_array": 16.0e-6*n,
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved/8000.0}}
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "korc_f32"
     if what.startswith("korc"):
@@ -353,6 +385,8 @@ if __name__ == "__main__":
         out = absorption()
     elif what.startswith("deposition"):
         out = deposition(what[len("deposition_"):] or "both")
+    elif what == "hand_over":
+        out = hand_over()
     else:
         raise SystemExit("unknown workload")
     print(json.dumps(out))

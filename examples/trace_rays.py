@@ -6,6 +6,7 @@ with a record every `sub_steps`, result<rank>.nc) on the MI355X backend.
     python examples/trace_rays.py --rays 100000 --steps 1000 --sub-steps 100 [--output /tmp/rays]
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4
+    python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4 --one-pass
     python examples/trace_rays.py --equilibrium vmec --rays 20000 --steps 10 --sub-steps 2 --output /tmp/vmec_rays
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/trace_rays.py ...
 
@@ -15,6 +16,8 @@ With --absorption-model the two stages that follow the trace in graph_driver/xra
 the same file: calculate_power (kamp per stored record) and bin_power (power, d_power).  With --bins and
 --bin-box as well, bin_power also bins d_power on that grid as it goes (utilities/bin.py's profile, exact sums)
 and the rank writes <output>_bins<rank>.nc: its own rays' sums divided by its own ray count.
+With --one-pass as well the same work items run on every record while the trace holds it in device memory
+(graph_framework_amd/pipeline.py): same file, same bits, written once, and no pass over the file afterwards.
 """
 import argparse
 import os
@@ -55,10 +58,16 @@ def main():
     parser.add_argument("--bins", default=None, metavar="NX,NY,NZ",
                         help="with --absorption-model and --bin-box: the deposition profile of utilities/bin.py on this grid")
     parser.add_argument("--bin-box", default=None, metavar="X0,X1,Y0,Y1,Z0,Z1", help="the box the grid divides")
+    parser.add_argument("--one-pass", action="store_true",
+                        help="with --output and --absorption-model: kamp, power and the bins of every record while the rays are "
+                             "traced, instead of two more passes over the file")
     args = parser.parse_args()
     if (args.bins is None) != (args.bin_box is None):
         parser.error("--bins and --bin-box go together")
+    if args.one_pass and not (args.output and args.absorption_model):
+        parser.error("--one-pass needs --output and --absorption-model")
 
+    import numpy as np
     import torch
     from graph_framework_amd import distributed
     from graph_framework_amd.output import TrajectoryWriter
@@ -74,20 +83,52 @@ def main():
                                   dispersion=args.dispersion)
     residual = solve.init("kx")
     solve.compile()
-    writer = TrajectoryWriter(solve, "%s%d.nc" % (args.output, rank)) if args.output else None
+    path = "%s%d.nc" % (args.output, rank) if args.output else None
+
+    def deposition_grid():
+        """(context, grid, cells, edges) of --bins/--bin-box."""
+        from graph_framework_amd import Context
+        from graph_framework_amd.deposition import Deposition
+        cells = [int(v) for v in args.bins.split(",")]
+        box = [float(v) for v in args.bin_box.split(",")]
+        edges = [np.linspace(box[2*a], box[2*a + 1], cells[a] + 1) for a in range(3)]
+        context = Context(local_rank)
+        return context, Deposition(context, *edges), cells, edges
+
+    def write_deposition(context, deposition, cells, edges):
+        from graph_framework_amd.output import write_bins
+        counts = deposition.counts()
+        bins = deposition.read(end - begin)
+        deposition.close()
+        context.close()
+        write_bins("%s_bins%d.nc" % (args.output, rank), bins, *edges, **counts)
+        print("rank %d: deposition on %s cells: %d samples, %d outside, %d skipped; sum of bins %.6e"
+              % (rank, "x".join(str(c) for c in cells), counts["samples"], counts["outside"], counts["skipped"],
+                 float(bins.sum())))
+
+    grid = None
+    if args.one_pass:
+        from graph_framework_amd.pipeline import OnePass
+        grid = deposition_grid() if args.bins else None
+        writer = OnePass(solve.work.context, end - begin, path, model=args.absorption_model, index=local_rank,
+                         stream=solve.torch_stream.cuda_stream, deposition=grid[1] if grid else None)
+        write_step = writer.record
+    else:
+        writer = TrajectoryWriter(solve, path) if args.output else None
+        write_step = writer.write_step if writer else None
     if writer:
-        writer.write_step()
+        write_step()
 
     start = time.perf_counter()
     for step in range(args.steps):
         solve.step()
         if writer and (step + 1) % args.sub_steps == 0:
-            writer.write_step()
+            write_step()
     host = solve.sync_host()
     elapsed = time.perf_counter() - start
+    after = time.perf_counter()
     if writer:
         writer.close()
-    import numpy as np
     lost = int((~np.isfinite(host["x"])).sum())          # rays the reference graph itself drives to NaN
     print("rank %d: %d rays, Newton %d iterations (max residual %.3e), %d steps in %.3f s = %.3e ray-steps/s; "
           "x in [%.4f, %.4f], %d rays non-finite, status flags %d"
@@ -95,33 +136,21 @@ def main():
              (end - begin)*args.steps/elapsed, np.nanmin(host["x"]), np.nanmax(host["x"]), lost,
              solve.work.context.flags()))
     if writer and args.absorption_model:
-        from graph_framework_amd.absorption import bin_power, run_absorption
         from graph_framework_amd.output import ResultFile
         solve.work.context.close()
-        path = "%s%d.nc" % (args.output, rank)
         records = args.steps//args.sub_steps
-        start = time.perf_counter()
-        run_absorption(path, records, index=local_rank, model=args.absorption_model)
-        context = deposition = None
-        if args.bins:
-            from graph_framework_amd import Context
-            from graph_framework_amd.deposition import Deposition
-            cells = [int(v) for v in args.bins.split(",")]
-            box = [float(v) for v in args.bin_box.split(",")]
-            edges = [np.linspace(box[2*a], box[2*a + 1], cells[a] + 1) for a in range(3)]
-            context = Context(local_rank)
-            deposition = Deposition(context, *edges)
-        bin_power(path, records, index=local_rank, deposition=deposition)
-        if deposition:
-            from graph_framework_amd.output import write_bins
-            counts = deposition.counts()
-            bins = deposition.read(end - begin)
-            deposition.close()
-            context.close()
-            write_bins("%s_bins%d.nc" % (args.output, rank), bins, *edges, **counts)
-            print("rank %d: deposition on %s cells: %d samples, %d outside, %d skipped; sum of bins %.6e"
-                  % (rank, "x".join(str(c) for c in cells), counts["samples"], counts["outside"], counts["skipped"],
-                     float(bins.sum())))
+        if args.one_pass:
+            start = after                                        # what is left after the trace: the last writes, the grid
+            if grid:
+                write_deposition(*grid)
+        else:
+            from graph_framework_amd.absorption import bin_power, run_absorption
+            start = time.perf_counter()
+            run_absorption(path, records, index=local_rank, model=args.absorption_model)
+            grid = deposition_grid() if args.bins else None
+            bin_power(path, records, index=local_rank, deposition=grid[1] if grid else None)
+            if grid:
+                write_deposition(*grid)
         elapsed = time.perf_counter() - start
         result = ResultFile(path)
         power = result.read("power", records)

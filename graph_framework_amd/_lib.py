@@ -31,6 +31,12 @@ class KernelInfo(ctypes.Structure):
                 ("name", ctypes.c_char*64)]
 
 
+class HandOverEntry(ctypes.Structure):
+    """struct gfhip_hand_over_entry (include/gf_hip.h)."""
+    _fields_ = [("to_key", ctypes.c_uint64), ("from_key", ctypes.c_uint64),
+                ("part", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 # Every symbol include/gf_hip.h declares: (name, restype, argtypes).
 _P, _S, _U64, _U32, _I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
 SYMBOLS = [
@@ -62,6 +68,7 @@ SYMBOLS = [
     ("gfhip_get_buffer_info", _I, [_P, _U64, ctypes.POINTER(_S), ctypes.POINTER(_U32)]),
     ("gfhip_get_host_buffer", _P, [_P, _U64, ctypes.POINTER(_S)]),
     ("gfhip_set_buffer", _I, [_P, _U64, _P, _S, _U32]),
+    ("gfhip_hand_over", _I, [_P, _P, ctypes.POINTER(HandOverEntry), _S]),
     ("gfhip_kernel_get_info", _I, [_P, ctypes.POINTER(KernelInfo)]),
     ("gfhip_generate_source", _P, [_P, _S, ctypes.POINTER(_U64)]),
     ("gfhip_generate_piece_source", _I, [_P, _S, _U32, ctypes.POINTER(_P), ctypes.POINTER(_U64)]),

@@ -49,17 +49,44 @@ class _Writer:
         self.thread.start()
 
 
+def absorption_work(num_rays, model="weak_damping", index=0, stream=None, items=None, tolerance=1.0e-30, max_iterations=1000):
+    """The manager of an absorption model over `num_rays` rays, not compiled yet: (work, host, newton).  `host` holds the
+    complex initial values of the inputs (zeros); `newton` is root_find's converge item, None for weak_damping.
+    items: GFIR that replaces an exported workload, {"weak_damping"} or {"init", "loss", "final"}."""
+    items = items or {}
+    work = Manager(index, stream)
+    zeros = np.zeros(num_rays, dtype=np.complex128)
+    host = {name: zeros.copy() for name in WEAK_DAMPING_INPUTS}
+    if model != "root_find":
+        work.add_item(items.get("weak_damping") or workload("weak_damping_kimg_kernel", "c64"), WEAK_DAMPING_INPUTS, [],
+                      num_rays, host)
+        return work, host, None
+    first = WEAK_DAMPING_INPUTS[:7]                                        # kamp kx ky kz x y z, absorption.hpp:170-178
+    work.add_item(items.get("init") or workload("root_find_init_kernel", "c64"), first, [], num_rays, host)
+    newton = work.add_converge_item(items.get("loss") or workload("root_find_loss_kernel", "c64"),
+                                    WEAK_DAMPING_INPUTS, ["root_find_residual"], num_rays, host, tolerance, max_iterations)
+    work.add_item(items.get("final") or workload("root_find_final_kamp", "c64"), first, [], num_rays, host)
+    return work, host, newton
+
+
+def power_work(num_rays, index=0, stream=None, item=None):
+    """bin_power's manager over `num_rays` rays, not compiled yet: (work, host, item).  power starts at 1, d_power and
+    k_sum at 0 (xrays.cpp:704-705)."""
+    work = Manager(index, stream)
+    host = {name: np.zeros(num_rays) for name in POWER_INPUTS}
+    host["power"][:] = 1.0                                                  # xrays.cpp:704-705
+    item = work.add_item(item or workload("power", "f64"), POWER_INPUTS, ["d_power"], num_rays, host)
+    return work, host, item
+
+
 class WeakDamping:
     """absorption::weak_damping<std::complex<double>, true> (absorption.hpp:325-470)."""
 
     def __init__(self, filename, index=0, stream=None, item=None):
         self.file = ResultFile(filename)                                    # result_file(filename): opened for update
         self.num_rays = self.file.num_rays
-        self.work = Manager(index, stream)
-        zeros = np.zeros(self.num_rays, dtype=np.complex128)
-        self.host = {name: zeros.copy() for name in WEAK_DAMPING_INPUTS}
-        self.item = self.work.add_item(item or workload("weak_damping_kimg_kernel", "c64"), WEAK_DAMPING_INPUTS, [],
-                                       self.num_rays, self.host)
+        self.work, self.host, _ = absorption_work(self.num_rays, "weak_damping", index, stream, {"weak_damping": item})
+        self.item = self.work.items[0]
         self.sync = _Writer()
 
     def compile(self):
@@ -95,18 +122,10 @@ class RootFinder(WeakDamping):
     (`final_kamp`)."""
 
     def __init__(self, filename, index=0, stream=None, items=None, tolerance=1.0e-30, max_iterations=1000):
-        items = items or {}
         self.file = ResultFile(filename)
         self.num_rays = self.file.num_rays
-        self.work = Manager(index, stream)
-        zeros = np.zeros(self.num_rays, dtype=np.complex128)
-        self.host = {name: zeros.copy() for name in WEAK_DAMPING_INPUTS}
-        first = WEAK_DAMPING_INPUTS[:7]                                    # kamp kx ky kz x y z, absorption.hpp:170-178
-        self.work.add_item(items.get("init") or workload("root_find_init_kernel", "c64"), first, [], self.num_rays, self.host)
-        self.newton = self.work.add_converge_item(items.get("loss") or workload("root_find_loss_kernel", "c64"),
-                                                  WEAK_DAMPING_INPUTS, ["root_find_residual"], self.num_rays, self.host,
-                                                  tolerance, max_iterations)
-        self.work.add_item(items.get("final") or workload("root_find_final_kamp", "c64"), first, [], self.num_rays, self.host)
+        self.work, self.host, self.newton = absorption_work(self.num_rays, "root_find", index, stream, items,
+                                                            tolerance, max_iterations)
         self.iterations = []
         self.sync = _Writer()
 
@@ -134,10 +153,7 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
     pass over it — and the exact state is merged into `deposition` at the end."""
     file = ResultFile(filename)
     n = file.num_rays
-    work = Manager(index, stream)
-    host = {name: np.zeros(n) for name in POWER_INPUTS}
-    host["power"][:] = 1.0                                                  # xrays.cpp:704-705
-    item = work.add_item(item or workload("power", "f64"), POWER_INPUTS, ["d_power"], n, host)
+    work, host, item = power_work(n, index, stream, item)
     work.compile()
     file.create_variable("power")
     file.create_variable("d_power")

@@ -141,12 +141,24 @@ class Context:
         return pointer, count.value
 
     def set_buffer(self, key, tensor):
-        """Adopt a contiguous torch CUDA tensor (float32/float64) as the buffer for `key`."""
+        """Adopt a contiguous torch CUDA tensor (float32/float64/complex64/complex128) as the buffer for `key`."""
         import torch
         assert tensor.is_cuda and tensor.is_contiguous()
-        dtype = {torch.float32: _lib.GFIR_F32, torch.float64: _lib.GFIR_F64}[tensor.dtype]
+        dtype = {torch.float32: _lib.GFIR_F32, torch.float64: _lib.GFIR_F64,
+                 torch.complex64: _lib.GFIR_C32, torch.complex128: _lib.GFIR_C64}[tensor.dtype]
         self._keepalive.append(tensor)
         self._check(self.lib.gfhip_set_buffer(self.handle, key_of(key), tensor.data_ptr(), tensor.numel(), dtype))
+
+    def hand_over(self, source, entries):
+        """gfhip_hand_over (include/gf_hip.h): buffers of the context `source` into buffers of this one, on the
+        device and in one launch, without waiting for it.  entries: (to_key, from_key) or (to_key, from_key, part);
+        a real source widens into a complex destination (imaginary parts +0.0), part = 0/1 takes the real/imaginary
+        parts of a complex source into a real destination."""
+        table = (_lib.HandOverEntry*max(len(entries), 1))()
+        for slot, entry in zip(table, entries):
+            slot.to_key, slot.from_key = key_of(entry[0]), key_of(entry[1])
+            slot.part = int(entry[2]) if len(entry) > 2 else 0
+        self._check(self.lib.gfhip_hand_over(self.handle, source.handle, table, len(entries)))
 
     def enable_timing(self, enable=True, every=1):
         """HIP events around every `every`-th launch of each kernel (see Kernel.timing)."""

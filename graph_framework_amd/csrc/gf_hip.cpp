@@ -33,6 +33,7 @@
 #include "plan.hpp"
 
 #include "converge_state.hpp"
+#include "hand_over.hpp"
 #include "superacc.hpp"
 
 namespace gfhip {
@@ -145,6 +146,7 @@ struct gfhip_context {
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
     unsigned int timing = 0;                       // 0 = off, N = events around every Nth launch of a kernel
+    event_ptr hand_over_before, hand_over_after;   // order gfhip_hand_over into this context from another stream (made on first use)
 
     int fail(const std::string &message) {
         error = message;
@@ -632,7 +634,11 @@ static int ensure_buffer(gfhip_context *ctx, const uint64_t key, const size_t co
         GFHIP_TRY(ctx, allocate(b.owned, bytes ? bytes : 8), "hipMalloc(buffer)");
         b.pointer = b.owned.get();
         if (!init || init_count < count) {
-            GFHIP_TRY(ctx, hipMemset(b.pointer, 0, bytes), "hipMemset(buffer)");
+//  On the context's stream and finished before anything else: hipMemset returns before the fill of device memory has
+//  run, on the null stream, which the context's non-blocking stream is not ordered with; an upload queued right behind
+//  the allocation (gfhip_copy_to_device) could land first and be zeroed.
+            GFHIP_TRY(ctx, hipMemsetAsync(b.pointer, 0, bytes, ctx->stream), "hipMemset(buffer)");
+            GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
         }
         if (init && init_count) {
             GFHIP_TRY(ctx, hipMemcpy(b.pointer, init, init_count*esize, hipMemcpyHostToDevice), "hipMemcpy(init)");
@@ -1384,6 +1390,79 @@ extern "C" int gfhip_set_buffer(gfhip_context *ctx, uint64_t key, void *device_p
     b.pointer = device_pointer;
     b.count = count;
     b.dtype = dtype;
+    return 0;
+}
+
+//  gfhip_hand_over: arrays from `from`'s buffers to `to`'s in one launch (hand_over.hip).  Everything is checked
+//  before anything is queued; the failure is left in both contexts.
+static int hand_over_fail(gfhip_context *to, gfhip_context *from, const std::string &message) {
+    from->fail(message);
+    return to->fail(message);
+}
+
+extern "C" int gfhip_hand_over(gfhip_context *to, gfhip_context *from, const struct gfhip_hand_over_entry *entries, size_t count) {
+    if (!to || !from || (!entries && count)) {
+        const char *message = "gfhip_hand_over: null argument";
+        creation_error = message;
+        if (to) to->fail(message);
+        if (from) from->fail(message);
+        return 1;
+    }
+    if (to->device != from->device) return hand_over_fail(to, from, "gfhip_hand_over: the contexts are on different devices");
+    std::vector<gfhip::hand_over_slot> slots;
+    slots.reserve(count);
+    for (size_t e = 0; e < count; e++) {
+        const gfhip_hand_over_entry &entry = entries[e];
+        const std::string where = "gfhip_hand_over: entry " + std::to_string(e) + ": ";
+        if (entry.reserved) return hand_over_fail(to, from, where + "reserved is not 0");
+        const auto target = to->buffers.find(entry.to_key);
+        const auto source = from->buffers.find(entry.from_key);
+        if (target == to->buffers.end()) return hand_over_fail(to, from, where + "unknown destination key");
+        if (source == from->buffers.end()) return hand_over_fail(to, from, where + "unknown source key");
+        const buffer &t = target->second, &f = source->second;
+        if (t.count != f.count) return hand_over_fail(to, from, where + "the buffers differ in element count");
+        const bool t_wide = t.dtype == GFIR_F64 || t.dtype == GFIR_C64, f_wide = f.dtype == GFIR_F64 || f.dtype == GFIR_C64;
+        const bool t_complex = t.dtype == GFIR_C32 || t.dtype == GFIR_C64, f_complex = f.dtype == GFIR_C32 || f.dtype == GFIR_C64;
+        if (t_wide != f_wide) return hand_over_fail(to, from, where + "the buffers differ in precision");
+        if (entry.part > 1) return hand_over_fail(to, from, where + "part is 0 (real) or 1 (imaginary)");
+        if (entry.part && !(f_complex && !t_complex)) {
+            return hand_over_fail(to, from, where + "part = 1 needs a complex source and a real destination");
+        }
+        gfhip::hand_over_slot slot = {t.pointer, f.pointer, f.count, 0, 0};
+        slot.mode = (f_complex == t_complex ? gfhip::hand_over_copy : (t_complex ? gfhip::hand_over_widen : gfhip::hand_over_part))
+                  | (f_wide ? gfhip::hand_over_wide : 0u) | (f_complex && t_complex ? gfhip::hand_over_complex : 0u)
+                  | (entry.part ? gfhip::hand_over_imaginary : 0u);
+        if (gfhip::hand_over_vector_ok(slot.mode, slot.to, slot.from)) slot.mode |= gfhip::hand_over_vector;
+        if (slot.count) slots.push_back(slot);
+    }
+//  Both contexts settled: passes that ran ahead of their caller are not handed over, nor overwritten later.
+    if (enter(to)) return hand_over_fail(to, from, std::string(to->error));
+    if (enter(from)) return hand_over_fail(to, from, std::string(from->error));
+    if (slots.empty()) return 0;
+//  On the source's stream: behind the kernels that wrote the sources and before those that overwrite them.  Another
+//  stream on the destination's side: what it has queued may still read the destinations, and what it queues next waits.
+    const bool two_streams = to->stream != from->stream;
+    if (two_streams) {
+        for (event_ptr *event : {&to->hand_over_before, &to->hand_over_after}) {
+            if (*event) continue;
+            hipEvent_t made = nullptr;
+            GFHIP_TRY(to, hipEventCreateWithFlags(&made, hipEventDisableTiming), "hipEventCreate");
+            event->reset(made);
+        }
+        GFHIP_TRY(to, hipEventRecord(to->hand_over_before.get(), to->stream), "hipEventRecord");
+        GFHIP_TRY(to, hipStreamWaitEvent(from->stream, to->hand_over_before.get(), 0), "hipStreamWaitEvent");
+    }
+    for (size_t first = 0; first < slots.size(); first += gfhip::hand_over_table_size) {
+        gfhip::hand_over_table table = {};
+        const unsigned int used = static_cast<unsigned int> (std::min<size_t> (slots.size() - first, gfhip::hand_over_table_size));
+        std::copy(slots.begin() + first, slots.begin() + first + used, table.slot);
+        gfhip::launch_hand_over(table, used, from->num_cus, from->stream);
+        if (from->check(hipGetLastError(), "hand-over launch")) return hand_over_fail(to, from, std::string(from->error));
+    }
+    if (two_streams) {
+        GFHIP_TRY(to, hipEventRecord(to->hand_over_after.get(), from->stream), "hipEventRecord");
+        GFHIP_TRY(to, hipStreamWaitEvent(to->stream, to->hand_over_after.get(), 0), "hipStreamWaitEvent");
+    }
     return 0;
 }
 

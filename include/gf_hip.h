@@ -205,6 +205,38 @@ void *gfhip_get_host_buffer(gfhip_context *ctx, uint64_t key, size_t *count);
  * buffer for `key`; the context will not free it. */
 int gfhip_set_buffer(gfhip_context *ctx, uint64_t key, void *device_pointer, size_t count, uint32_t dtype);
 
+/* Hand arrays over from the buffers of one context to those of another (or of the same one) on the device, in
+ * one launch of a hand-written streaming kernel (csrc/hand_over.hip): element i of `from_key`'s buffer in `from`
+ * becomes element i of `to_key`'s buffer in `to`, for every entry.  This is what lets the stages of a pipeline,
+ * each with a context of its own because the same variable is real in one item and complex in the next
+ * (absorption.hpp:411-422 against solver.hpp:304-313), feed each other without a file or the host in between.
+ * Values move bit for bit, never through arithmetic (NaN payloads, -0.0, infinities, subnormals unchanged):
+ *   F64->F64, F32->F32, C64->C64, C32->C32   copied;
+ *   F64->C64, F32->C32                       real part = source, imaginary part = +0.0 (what output.hpp:305,
+ *                                            :425-428 does when a complex data_set reads a real variable);
+ *   C64->F64, C32->F32                       the real parts (part = 0) or the imaginary parts (part = 1,
+ *                                            reference_imag_variable).
+ * Everything else fails with a message in gfhip_last_error of both contexts and launches NOTHING, whatever the
+ * other entries are: a change of precision, part > 1, part = 1 where the source is not complex or the
+ * destination not real, reserved != 0, an unknown key, buffers of different element counts, contexts on different
+ * devices, a null context or a null `entries` with count > 0 (the message is also in gfhip_last_error(NULL)).
+ * Ordering: both contexts are entered first, so passes that ran ahead of gfhip_run_max's caller are taken back
+ * before anything is handed over.  The launch goes on `from`'s stream, behind the kernels that wrote the sources
+ * and before the ones that overwrite them.  If `to` has another stream, `from`'s stream first waits for what
+ * `to`'s has queued (it may still read the destinations) and `to`'s stream then waits for the launch; with one
+ * shared stream no event is involved.  The call does not synchronise the host.  More than 16 entries (the
+ * kernel's pointer table) take one launch per 16; entries of zero elements take none.  `to` == `from` is allowed
+ * (x -> x_last).  Buffers adopted with gfhip_set_buffer need only the alignment of their elements: the 16-byte
+ * accesses are chosen per entry from the pointers. */
+struct gfhip_hand_over_entry {
+    uint64_t to_key;      /* buffer of `to`   */
+    uint64_t from_key;    /* buffer of `from` */
+    uint32_t part;        /* complex -> real only: 0 = real parts, 1 = imaginary parts; else 0 */
+    uint32_t reserved;    /* 0 */
+};
+int gfhip_hand_over(gfhip_context *to, gfhip_context *from,
+                    const struct gfhip_hand_over_entry *entries, size_t count);
+
 /* Introspection used by hosts, tests and the benchmark. */
 struct gfhip_kernel_info {
     uint32_t dtype;                 /* enum gfir_dtype */
