@@ -7,6 +7,7 @@ with a record every `sub_steps`, result<rank>.nc) on the MI355X backend.
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4 --one-pass
+    python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --one-pass
     python examples/trace_rays.py --equilibrium vmec --rays 20000 --steps 10 --sub-steps 2 --output /tmp/vmec_rays
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/trace_rays.py ...
 
@@ -16,6 +17,8 @@ With --absorption-model the two stages that follow the trace in graph_driver/xra
 the same file: calculate_power (kamp per stored record) and bin_power (power, d_power).  With --bins and
 --bin-box as well, bin_power also bins d_power on that grid as it goes (utilities/bin.py's profile, exact sums)
 and the rank writes <output>_bins<rank>.nc: its own rays' sums divided by its own ray count.
+With --flux-bins and --flux-tables (alone or next to --bins) d_power is also binned on flux surfaces
+(graph_framework_amd/flux.py) and the rank writes <output>_flux<rank>.nc.
 With --one-pass as well the same work items run on every record while the trace holds it in device memory
 (graph_framework_amd/pipeline.py): same file, same bits, written once, and no pass over the file afterwards.
 """
@@ -58,12 +61,22 @@ def main():
     parser.add_argument("--bins", default=None, metavar="NX,NY,NZ",
                         help="with --absorption-model and --bin-box: the deposition profile of utilities/bin.py on this grid")
     parser.add_argument("--bin-box", default=None, metavar="X0,X1,Y0,Y1,Z0,Z1", help="the box the grid divides")
+    parser.add_argument("--flux-bins", type=int, default=None, metavar="N",
+                        help="with --absorption-model and --flux-tables: absorbed power on N uniform cells of the flux label")
+    parser.add_argument("--flux-tables", default=None, metavar="FILE.npz",
+                        help="the EFIT tables under efit.nc's dataset names (psi_c00 .. psi_c33, rmin, dr, zmin, dz, psimin, dpsi)")
+    parser.add_argument("--flux-range", default="0,1", metavar="LOW,HIGH", help="the label range the cells divide")
+    parser.add_argument("--flux-sqrt", action="store_true", help="label sqrt((psi - psimin)/span) instead of (psi - psimin)/span")
     parser.add_argument("--one-pass", action="store_true",
                         help="with --output and --absorption-model: kamp, power and the bins of every record while the rays are "
                              "traced, instead of two more passes over the file")
     args = parser.parse_args()
     if (args.bins is None) != (args.bin_box is None):
         parser.error("--bins and --bin-box go together")
+    if (args.flux_bins is None) != (args.flux_tables is None):
+        parser.error("--flux-bins and --flux-tables go together")
+    if args.flux_bins is not None and not (args.output and args.absorption_model):
+        parser.error("--flux-bins needs --output and --absorption-model")
     if args.one_pass and not (args.output and args.absorption_model):
         parser.error("--one-pass needs --output and --absorption-model")
 
@@ -106,12 +119,35 @@ def main():
               % (rank, "x".join(str(c) for c in cells), counts["samples"], counts["outside"], counts["skipped"],
                  float(bins.sum())))
 
+    def flux_profile():
+        """(context, profile) of --flux-bins/--flux-tables/--flux-range/--flux-sqrt."""
+        from graph_framework_amd import Context
+        from graph_framework_amd.flux import FluxProfile
+        low, high = (float(v) for v in args.flux_range.split(","))
+        tables = dict(np.load(args.flux_tables))
+        context = Context(local_rank)
+        return context, FluxProfile(context, tables, np.linspace(low, high, args.flux_bins + 1), sqrt_label=args.flux_sqrt)
+
+    def write_flux(context, profile):
+        from graph_framework_amd.output import write_flux_bins
+        counts = profile.counts()
+        bins = profile.read(end - begin)
+        edges, psi0, span, kind = profile.edges, profile.psi0, profile.span, profile.label_kind
+        profile.close()
+        context.close()
+        write_flux_bins("%s_flux%d.nc" % (args.output, rank), bins, edges, psi0, span, kind, **counts)
+        print("rank %d: flux profile on %d cells of %s: %d samples, %d outside, %d skipped; sum of bins %.6e"
+              % (rank, bins.size, kind, counts["samples"], counts["outside"], counts["skipped"], float(bins.sum())))
+
     grid = None
+    surfaces = None
     if args.one_pass:
         from graph_framework_amd.pipeline import OnePass
         grid = deposition_grid() if args.bins else None
+        surfaces = flux_profile() if args.flux_bins else None
         writer = OnePass(solve.work.context, end - begin, path, model=args.absorption_model, index=local_rank,
-                         stream=solve.torch_stream.cuda_stream, deposition=grid[1] if grid else None)
+                         stream=solve.torch_stream.cuda_stream, deposition=grid[1] if grid else None,
+                         flux=surfaces[1] if surfaces else None)
         write_step = writer.record
     else:
         writer = TrajectoryWriter(solve, path) if args.output else None
@@ -143,14 +179,20 @@ def main():
             start = after                                        # what is left after the trace: the last writes, the grid
             if grid:
                 write_deposition(*grid)
+            if surfaces:
+                write_flux(*surfaces)
         else:
             from graph_framework_amd.absorption import bin_power, run_absorption
             start = time.perf_counter()
             run_absorption(path, records, index=local_rank, model=args.absorption_model)
             grid = deposition_grid() if args.bins else None
-            bin_power(path, records, index=local_rank, deposition=grid[1] if grid else None)
+            surfaces = flux_profile() if args.flux_bins else None
+            bin_power(path, records, index=local_rank, deposition=grid[1] if grid else None,
+                      flux=surfaces[1] if surfaces else None)
             if grid:
                 write_deposition(*grid)
+            if surfaces:
+                write_flux(*surfaces)
         elapsed = time.perf_counter() - start
         result = ResultFile(path)
         power = result.read("power", records)

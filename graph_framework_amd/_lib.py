@@ -88,6 +88,16 @@ SYMBOLS = [
     ("gfhip_bins_merge", _I, [_P, _P, _U64, _U64, _U64]),
     ("gfhip_bins_read", _I, [_P, ctypes.c_double, _P]),
     ("gfhip_bins_destroy", None, [_P]),
+    ("gfhip_flux_create", _P, [_P, _P, _P, _S]),
+    ("gfhip_flux_add", _I, [_P, _U64, _U64, _U64, _U64, _S]),
+    ("gfhip_flux_label", _I, [_P, _U64, _U64, _U64, _U64, _S]),
+    ("gfhip_flux_counts", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("gfhip_flux_state", _I, [_P, _P]),
+    ("gfhip_flux_merge", _I, [_P, _P, _S, _U64, _U64, _U64]),
+    ("gfhip_flux_read", _I, [_P, ctypes.c_double, _P]),
+    ("gfhip_flux_info", _I, [_P, _P]),
+    ("gfhip_flux_destroy", None, [_P]),
+    ("gfhip_flux_label_host", _I, [_P, _P, _P, _P, _S, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 

@@ -144,13 +144,15 @@ def run_absorption(filename, num_steps, index=0, model="weak_damping"):
     return power
 
 
-def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=None):
+def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=None, flux=None):
     """bin_power's per-shard body (xrays.cpp:694-786).
 
     deposition: a deposition.Deposition (on any context).  Every record's x, y, z and d_power are then binned on
     its grid from the device buffers, right behind the `power` item on the same stream — what
     deposition.bin_deposition would find in the file afterwards, record 0 (d_power = 0) included, without a second
-    pass over it — and the exact state is merged into `deposition` at the end."""
+    pass over it — and the exact state is merged into `deposition` at the end.
+    flux: a flux.FluxProfile (on any context), alone or next to `deposition`: the same records binned on its flux
+    surfaces, the exact state merged into it at the end."""
     file = ResultFile(filename)
     n = file.num_rays
     work, host, item = power_work(n, index, stream, item)
@@ -163,12 +165,16 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
     for name in ("x", "y", "z"):                                            # dataset.read(file, 0) ... :767-771
         host[name][:] = file.read(name, 0)
         host[name + "_last"][:] = host[name]
-    local = None
+    grids = []                                                              # (the caller's, its local twin on this context)
     if deposition is not None:
         from .deposition import Deposition
-        local = Deposition(work.context, *deposition.edges)
+        grids.append((deposition, Deposition(work.context, *deposition.edges)))
+    if flux is not None:
+        grids.append((flux, flux.like(work.context)))
+    if grids:
         for name in ("x", "y", "z"):
             work.copy_to_device(name, host[name])
+    for _, local in grids:
         local.add("x", "y", "z", "d_power", n)
     work.wait()                                                             # mirrors hold the initial values
     file.write({"power": power.copy(), "d_power": d_power.copy()}, index=0)
@@ -182,7 +188,7 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
         host["kamp"][:] = file.read("kamp", j, part=1)                      # reference_imag_variable
         work.copy_to_device("kamp", host["kamp"])
         work.run()
-        if local is not None:
+        for _, local in grids:
             local.add("x", "y", "z", "d_power", n)
         sync.join()
         work.wait()
@@ -190,8 +196,8 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
         sync.start(lambda record=record, j=j: file.write(record, index=j))
     sync.join()
     file.close()
-    if local is not None:
-        deposition.merge(local.state(), **local.counts())
+    for target, local in grids:
+        target.merge(local.state(), **local.counts())
         local.close()
     work.context.close()
     return item

@@ -1,0 +1,93 @@
+//------------------------------------------------------------------------------
+///  @file flux_label.hpp
+///  @brief The flux label of a point (x, y, z) from the EFIT psi spline, host and device.
+///
+///  The spline is evaluated in the representation the tracer itself uses: in every cell of the (R, Z) table a
+///  bicubic polynomial in the GLOBAL normalised coordinates tr = (R - rmin)/dr, tz = (z - zmin)/dz, whose integer
+///  parts are also the cell's indices.  The arithmetic is fixed: every operation below is one IEEE fp64 operation,
+///  in this order, nothing fused (contraction is switched off here, whatever the translation unit's flags say), so
+///  the host, the device and the numpy model of the tests give the same bits:
+///
+///      R   = sqrt(x*x + y*y)
+///      tr  = (R - rmin)/dr          tz = (z - zmin)/dz
+///      inside the map  iff  tr >= 0 && tr < numr && tz >= 0 && tz < numz      (a NaN is outside)
+///      i = (int)tr, j = (int)tz, c[a][b] = psi_c<a><b>[i][j]
+///      col_a = ((c[a][3]*tz + c[a][2])*tz + c[a][1])*tz + c[a][0]             a = 0..3
+///      psi   = ((col_3*tr + col_2)*tr + col_1)*tr + col_0
+///      s     = (psi - psi0)/span
+///      label = s, or sqrt(s) when flag bit 0 is set (s < 0 gives NaN)
+///
+///  Unlike the tracer's gather the map does not clamp: a point off the table has no label (NaN).  Plain C++.
+//------------------------------------------------------------------------------
+#ifndef GFHIP_FLUX_LABEL_HPP
+#define GFHIP_FLUX_LABEL_HPP
+
+#include <math.h>
+#include <stdint.h>
+
+#include "superacc.hpp"                                // GFHIP_HD
+
+namespace gfhip {
+namespace flux {
+
+constexpr uint32_t flag_sqrt_label = 1u;               // label = sqrt(s)
+constexpr uint32_t flag_no_private_sums = 2u;          // flux_profile.hip: deposits go to the global state
+constexpr uint32_t known_flags = flag_sqrt_label | flag_no_private_sums;
+
+//  The scalars of a map; the coefficients travel separately (16 tables on the host, [cell][16] on the device).
+struct map {
+    double rmin, dr, zmin, dz;
+    double numr, numz;                                 // the table's extents as doubles: what tr and tz are compared with
+    unsigned long long columns;                        // numz: cell = i*columns + j
+    double psi0, span;
+    uint32_t flags;
+};
+
+//  The table cell of (x, y, z), i*numz + j, with the normalised coordinates it was found from; -1 outside the map.
+GFHIP_HD long long locate(const map &m, const double x, const double y, const double z, double &tr, double &tz) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double xx = x*x;
+    const double yy = y*y;
+    const double r = sqrt(xx + yy);
+    tr = (r - m.rmin)/m.dr;
+    tz = (z - m.zmin)/m.dz;
+    if (!(tr >= 0.0 && tr < m.numr && tz >= 0.0 && tz < m.numz)) return -1;
+    return static_cast<long long> (static_cast<int> (tr))*static_cast<long long> (m.columns) + static_cast<int> (tz);
+}
+
+//  psi from a cell's 16 coefficients, c[a*4 + b].
+GFHIP_HD double psi_of(const double *c, const double tr, const double tz) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double column[4];
+    for (int a = 0; a < 4; a++) {
+        double t = c[4*a + 3]*tz;
+        t = t + c[4*a + 2];
+        t = t*tz;
+        t = t + c[4*a + 1];
+        t = t*tz;
+        column[a] = t + c[4*a];
+    }
+    double p = column[3]*tr;
+    p = p + column[2];
+    p = p*tr;
+    p = p + column[1];
+    p = p*tr;
+    return p + column[0];
+}
+
+GFHIP_HD double label_of(const map &m, const double psi) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double s = (psi - m.psi0)/m.span;
+    return (m.flags & flag_sqrt_label) ? sqrt(s) : s;
+}
+
+}  // namespace flux
+}  // namespace gfhip
+
+#endif

@@ -24,6 +24,7 @@
 #include <limits>
 #include <map>
 #include <memory>
+#include <new>
 #include <optional>
 #include <string>
 #include <type_traits>
@@ -33,6 +34,7 @@
 #include "plan.hpp"
 
 #include "converge_state.hpp"
+#include "flux_label.hpp"
 #include "hand_over.hpp"
 #include "superacc.hpp"
 
@@ -49,6 +51,16 @@ void launch_deposit(const double *x, const double *y, const double *z, const dou
 void launch_bins_normalise(void *state, const size_t cells, hipStream_t stream);
 void launch_bins_round(const void *state, const size_t cells, const double divisor, double *bins, hipStream_t stream);
 void launch_bins_merge(void *state, const void *other, const size_t words, hipStream_t stream);
+//  flux_profile.hip
+void flux_launch_shape(const size_t cells, const bool allow_private, const unsigned int num_cus,
+                       bool *is_private, size_t *cap, unsigned int *block, size_t *max_workgroups, size_t *lds_bytes);
+hipError_t flux_prepare();
+void launch_flux_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
+                         const flux::map &m, const double *packed, const double *edges, const size_t cells, const double scale,
+                         const bool is_private, const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                         void *state, unsigned long long *counters, hipStream_t stream);
+void launch_flux_label(const double *x, const double *y, const double *z, const size_t count, const flux::map &m,
+                       const double *packed, double *label, hipStream_t stream);
 }
 
 namespace {
@@ -142,6 +154,7 @@ struct gfhip_context {
     std::map<uint64_t, device_ptr<>> random_states;    // MT19937 states per random_state node (raw bytes)
     std::vector<std::unique_ptr<gfhip_kernel>> kernels;
     std::vector<std::unique_ptr<gfhip_bins>> bins;     // deposition grids (gfhip_bins_create), until gfhip_bins_destroy
+    std::vector<std::unique_ptr<gfhip_flux>> fluxes;   // flux profiles (gfhip_flux_create), until gfhip_flux_destroy
     std::string error;
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
@@ -215,6 +228,22 @@ struct gfhip_bins {
     device_ptr<unsigned long long> counters;           // samples, outside, skipped
     device_ptr<double> rounded;                        // what gfhip_bins_read copies out (allocated by the first read)
     uint64_t pending = 0;                              // deposits since the state was last canonical
+};
+
+//  A flux-surface profile: per cell the 67 limbs of superacc.hpp, [cell][limb]; the psi tables as [table cell][16].
+struct gfhip_flux {
+    gfhip_context *ctx = nullptr;
+    gfhip::flux::map map = {};
+    size_t cells = 0;
+    double scale = 0.0;                                // cells/(last edge - first edge)
+    device_ptr<double> packed, edges;
+    device_ptr<> state;
+    device_ptr<unsigned long long> counters;           // samples, outside, skipped
+    device_ptr<double> rounded;
+    uint64_t pending = 0;                              // deposits since the state was last canonical
+    bool is_private = false;
+    size_t cap = 0, max_workgroups = 0, lds_bytes = 0;
+    unsigned int block = 0;
 };
 
 #define GFHIP_TRY(ctx, call, what) do { if ((ctx)->check((call), (what))) return 1; } while (0)
@@ -1680,6 +1709,258 @@ extern "C" int gfhip_bins_read(gfhip_bins *b, double divisor, double *bins) {
     GFHIP_TRY(ctx, hipMemcpyAsync(bins, b->rounded.get(), b->cells*sizeof(double), hipMemcpyDeviceToHost, ctx->stream),
               "hipMemcpyAsync(rounded bins)");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+//  Flux profiles (flux_profile.hip, flux_label.hpp).  At most 4096 cells: the edges are staged in LDS on both paths.
+static const size_t flux_cell_limit = 4096;
+
+//  The scalars of a caller's map, or why it is refused.
+static const char *flux_map_of(const gfhip_flux_map *given, gfhip::flux::map &m) {
+    if (!given->coefficients) return "a flux map needs its 16 coefficient tables";
+    if (given->numr == 0 || given->numz == 0) return "a flux map needs numr >= 1 and numz >= 1";
+    const uint64_t table_limit = 1ull << 31;
+    if (given->numr > table_limit || given->numz > table_limit || given->numr*given->numz > table_limit) {
+        return "a flux map's table has at most 2^31 cells";
+    }
+    if (!std::isfinite(given->dr) || given->dr == 0.0 || !std::isfinite(given->dz) || given->dz == 0.0 ||
+        !std::isfinite(given->span) || given->span == 0.0) {
+        return "dr, dz and span of a flux map must be finite and non-zero";
+    }
+    if (!std::isfinite(given->rmin) || !std::isfinite(given->zmin) || !std::isfinite(given->psi0)) {
+        return "rmin, zmin and psi0 of a flux map must be finite";
+    }
+    if (given->flags & ~gfhip::flux::known_flags) return "unknown flag bits in a flux map";
+    if (given->reserved != 0) return "the reserved field of a flux map must be 0";
+    m.rmin = given->rmin;
+    m.dr = given->dr;
+    m.zmin = given->zmin;
+    m.dz = given->dz;
+    m.numr = static_cast<double> (given->numr);
+    m.numz = static_cast<double> (given->numz);
+    m.columns = given->numz;
+    m.psi0 = given->psi0;
+    m.span = given->span;
+    m.flags = given->flags;
+    return nullptr;
+}
+
+extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, size_t cells) {
+    if (!ctx) return nullptr;
+    if (!map || !edges) {
+        ctx->fail("a flux profile needs a map and edges");
+        return nullptr;
+    }
+    if (cells < 1 || cells > flux_cell_limit) {
+        ctx->fail("a flux profile has 1 to 4096 cells");
+        return nullptr;
+    }
+    for (size_t i = 0; i <= cells; i++) {
+        if (!std::isfinite(edges[i]) || (i && !(edges[i - 1] < edges[i]))) {
+            ctx->fail("the edges of a flux profile must be finite and strictly increasing");
+            return nullptr;
+        }
+    }
+    std::unique_ptr<gfhip_flux> f(new gfhip_flux);
+    if (const char *refused = flux_map_of(map, f->map)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    if (ctx->check(hipSetDevice(ctx->device), "hipSetDevice")) return nullptr;
+    f->ctx = ctx;
+    f->cells = cells;
+    f->scale = static_cast<double> (cells)/(edges[cells] - edges[0]);
+    gfhip::flux_launch_shape(cells, !(map->flags & gfhip::flux::flag_no_private_sums), ctx->num_cus, &f->is_private, &f->cap,
+                             &f->block, &f->max_workgroups, &f->lds_bytes);
+//  [table cell][16]: a lane's coefficients are one 128-byte line.
+    const size_t table = static_cast<size_t> (map->numr*map->numz);
+    std::vector<double> packed;
+    try {
+        packed.resize(table*16);
+    } catch (const std::bad_alloc &) {
+        ctx->fail("a flux map's tables do not fit the host's memory");
+        return nullptr;
+    }
+    for (size_t k = 0; k < 16; k++) {
+        const double *from = map->coefficients + k*table;
+        for (size_t at = 0; at < table; at++) packed[at*16 + k] = from[at];
+    }
+    const size_t bytes = cells*gfhip::superacc::limbs*sizeof(int64_t);
+    if (ctx->check(allocate(f->packed, packed.size()*sizeof(double)), "hipMalloc(flux tables)") ||
+        ctx->check(hipMemcpy(f->packed.get(), packed.data(), packed.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
+        ctx->check(allocate(f->edges, (cells + 1)*sizeof(double)), "hipMalloc(edges)") ||
+        ctx->check(hipMemcpy(f->edges.get(), edges, (cells + 1)*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
+        ctx->check(allocate(f->state, bytes), "hipMalloc(flux profile)") ||
+        ctx->check(hipMemset(f->state.get(), 0, bytes), "hipMemset(flux profile)") ||
+        ctx->check(allocate(f->counters, 3*sizeof(unsigned long long)), "hipMalloc(counters)") ||
+        ctx->check(hipMemset(f->counters.get(), 0, 3*sizeof(unsigned long long)), "hipMemset(counters)") ||
+        (f->is_private && ctx->check(gfhip::flux_prepare(), "hipFuncSetAttribute(flux deposit)"))) {
+        return nullptr;
+    }
+    ctx->fluxes.push_back(std::move(f));
+    return ctx->fluxes.back().get();
+}
+
+extern "C" void gfhip_flux_destroy(gfhip_flux *f) {
+    if (!f) return;
+    gfhip_context *ctx = f->ctx;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (auto it = ctx->fluxes.begin(); it != ctx->fluxes.end(); ++it) {
+        if (it->get() == f) {
+            ctx->fluxes.erase(it);
+            return;
+        }
+    }
+}
+
+static int flux_normalise(gfhip_flux *f) {
+    gfhip::launch_bins_normalise(f->state.get(), f->cells, f->ctx->stream);
+    f->pending = 0;
+    return f->ctx->check(hipGetLastError(), "normalise launch");
+}
+
+//  Four fp64 buffers of at least `count` elements, or the message; nothing is enqueued.
+static int flux_columns(gfhip_context *ctx, const uint64_t *keys, const size_t count, double **columns) {
+    for (int c = 0; c < 4; c++) {
+        const buffer *found = find_buffer(ctx, keys[c]);
+        if (!found) return 1;
+        if (found->dtype != GFIR_F64) return ctx->fail("a flux profile reads and writes fp64 buffers");
+        if (found->count < count) return ctx->fail("a flux profile buffer is shorter than the sample count");
+        columns[c] = static_cast<double *> (found->pointer);
+    }
+    return 0;
+}
+
+extern "C" int gfhip_flux_add(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count) {
+    if (!f) return 1;
+    gfhip_context *ctx = f->ctx;
+    const uint64_t keys[4] = {x_key, y_key, z_key, value_key};
+    double *columns[4];
+    if (flux_columns(ctx, keys, count, columns)) return 1;
+    if (enter(ctx)) return 1;
+//  At most 2^30 deposits between two normalisations (superacc.hpp); a private limb sees fewer than its launch.
+    for (size_t first = 0; first < count;) {
+        const size_t piece = std::min<size_t> (count - first, gfhip::superacc::deposits_per_normalise);
+        if (f->pending + piece > gfhip::superacc::deposits_per_normalise && flux_normalise(f)) return 1;
+        gfhip::launch_flux_deposit(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
+                                   f->map, f->packed.get(), f->edges.get(), f->cells, f->scale, f->is_private, f->block,
+                                   f->max_workgroups, f->lds_bytes, f->state.get(), f->counters.get(), ctx->stream);
+        GFHIP_TRY(ctx, hipGetLastError(), "flux deposit launch");
+        f->pending += piece;
+        first += piece;
+    }
+    return 0;
+}
+
+extern "C" int gfhip_flux_label(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t label_key, size_t count) {
+    if (!f) return 1;
+    gfhip_context *ctx = f->ctx;
+    const uint64_t keys[4] = {x_key, y_key, z_key, label_key};
+    double *columns[4];
+    if (flux_columns(ctx, keys, count, columns)) return 1;
+    if (enter(ctx)) return 1;
+    gfhip::launch_flux_label(columns[0], columns[1], columns[2], count, f->map, f->packed.get(), columns[3], ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "flux label launch");
+    return 0;
+}
+
+extern "C" int gfhip_flux_counts(gfhip_flux *f, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
+    if (!f) return 1;
+    gfhip_context *ctx = f->ctx;
+    if (enter(ctx)) return 1;
+    unsigned long long host[3] = {0, 0, 0};
+    GFHIP_TRY(ctx, hipMemcpyAsync(host, f->counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (samples) *samples = host[0];
+    if (outside) *outside = host[1];
+    if (skipped) *skipped = host[2];
+    return 0;
+}
+
+extern "C" int gfhip_flux_state(gfhip_flux *f, int64_t *limbs) {
+    if (!f) return 1;
+    gfhip_context *ctx = f->ctx;
+    if (!limbs) return ctx->fail("gfhip_flux_state needs a destination");
+    if (enter(ctx) || flux_normalise(f)) return 1;
+    GFHIP_TRY(ctx, hipMemcpyAsync(limbs, f->state.get(), f->cells*gfhip::superacc::limbs*sizeof(int64_t), hipMemcpyDeviceToHost,
+                                  ctx->stream), "hipMemcpyAsync(flux profile)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+extern "C" int gfhip_flux_merge(gfhip_flux *f, const int64_t *limbs, size_t cells, uint64_t samples, uint64_t outside, uint64_t skipped) {
+    if (!f) return 1;
+    gfhip_context *ctx = f->ctx;
+    if (!limbs) return ctx->fail("gfhip_flux_merge needs a state");
+    if (cells != f->cells) return ctx->fail("merge: a flux profile of another shape");
+    if (enter(ctx)) return 1;
+    const size_t words = f->cells*gfhip::superacc::limbs;
+    const unsigned long long counts[3] = {samples, outside, skipped};
+    device_ptr<> other;                                // the incoming limbs, then the three counts
+    GFHIP_TRY(ctx, allocate(other, (words + 3)*sizeof(int64_t)), "hipMalloc(merge)");
+    char *counts_at = static_cast<char *> (other.get()) + words*sizeof(int64_t);
+    GFHIP_TRY(ctx, hipMemcpyAsync(other.get(), limbs, words*sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
+    GFHIP_TRY(ctx, hipMemcpyAsync(counts_at, counts, sizeof(counts), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
+//  Canonical digits (below 2^32) on top of a state that 2^30 deposits may have reached: still inside a limb.
+    gfhip::launch_bins_merge(f->state.get(), other.get(), words, ctx->stream);
+    gfhip::launch_bins_merge(f->counters.get(), counts_at, 3, ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "merge launch");
+    if (flux_normalise(f)) return 1;
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // `other` is freed on return
+    return 0;
+}
+
+extern "C" int gfhip_flux_read(gfhip_flux *f, double divisor, double *values) {
+    if (!f) return 1;
+    gfhip_context *ctx = f->ctx;
+    if (!values) return ctx->fail("gfhip_flux_read needs a destination");
+    if (enter(ctx)) return 1;
+    if (!f->rounded) GFHIP_TRY(ctx, allocate(f->rounded, f->cells*sizeof(double)), "hipMalloc(rounded profile)");
+    if (flux_normalise(f)) return 1;
+    gfhip::launch_bins_round(f->state.get(), f->cells, divisor, f->rounded.get(), ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "round launch");
+    GFHIP_TRY(ctx, hipMemcpyAsync(values, f->rounded.get(), f->cells*sizeof(double), hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpyAsync(rounded profile)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+//  Not through enter(): it reads what gfhip_flux_create decided on the host and touches neither the device nor the stream.
+extern "C" int gfhip_flux_info(gfhip_flux *f, struct gfhip_flux_info *info) {
+    if (!f) return 1;
+    if (!info) return f->ctx->fail("gfhip_flux_info needs a destination");
+    info->private_sums = f->is_private ? 1u : 0u;
+    info->workgroup_size = f->block;
+    info->cap_cells = f->cap;
+    info->max_workgroups = f->max_workgroups;
+    info->lds_bytes = f->lds_bytes;
+    return 0;
+}
+
+//  Host side, no device: flux_label.hpp on the caller's 16 tables.
+extern "C" int gfhip_flux_label_host(const gfhip_flux_map *map, const double *x, const double *y, const double *z,
+                                     size_t count, double *label) {
+    if (!map || ((!x || !y || !z || !label) && count)) {
+        creation_error = "gfhip_flux_label_host needs a map, three coordinate arrays and a destination";
+        return 1;
+    }
+    gfhip::flux::map m;
+    if (const char *refused = flux_map_of(map, m)) {
+        creation_error = refused;
+        return 1;
+    }
+    const size_t table = static_cast<size_t> (map->numr*map->numz);
+    for (size_t s = 0; s < count; s++) {
+        double tr, tz, c[16];
+        const long long at = gfhip::flux::locate(m, x[s], y[s], z[s], tr, tz);
+        if (at < 0) {
+            label[s] = std::numeric_limits<double>::quiet_NaN();
+            continue;
+        }
+        for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
+        label[s] = gfhip::flux::label_of(m, gfhip::flux::psi_of(c, tr, tz));
+    }
     return 0;
 }
 

@@ -1,0 +1,187 @@
+"""Flux-surface profiles: absorbed power per flux surface, P(psi), on the device and exact.
+
+The 3-D grid of deposition.py is bin.py's picture; for a tokamak the result of a ray-tracing run is drawn over the flux
+label.  A FluxProfile labels every sample with s = (psi(R, z) - psi0)/span (or its square root) from the EFIT psi spline,
+in the fixed arithmetic of csrc/flux_label.hpp, finds the label's cell among the edges by the rule of the 3-D grid
+(edge[i] <= label < edge[i+1]) and adds the value to that cell's superaccumulator (csrc/superacc.hpp).  A profile is small
+enough for every workgroup to sum its deposits in LDS before they reach memory (csrc/flux_profile.hip); the state is the
+same bytes with and without that, and for any order of samples, records, files or shards.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from .backend import GfHipError, key_of
+from .output import ResultFile, write_flux_bins
+
+LIMBS = 67
+SQRT_LABEL = 1
+NO_PRIVATE_SUMS = 2
+TABLE_NAMES = tuple("psi_c%d%d" % (a, b) for a in range(4) for b in range(4))
+
+
+class _Map(ctypes.Structure):
+    _fields_ = [("rmin", ctypes.c_double), ("dr", ctypes.c_double), ("zmin", ctypes.c_double), ("dz", ctypes.c_double),
+                ("numr", ctypes.c_uint64), ("numz", ctypes.c_uint64), ("coefficients", ctypes.c_void_p),
+                ("psi0", ctypes.c_double), ("span", ctypes.c_double), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class _Info(ctypes.Structure):
+    _fields_ = [("private_sums", ctypes.c_uint32), ("workgroup_size", ctypes.c_uint32), ("cap_cells", ctypes.c_uint64),
+                ("max_workgroups", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64)]
+
+
+def default_range(tables):
+    """(psi0, span) of the reference's profile tables: the axis value psimin and dpsi*(numpsi - 1), axis to edge."""
+    return float(tables["psimin"]), float(tables["dpsi"])*(np.asarray(tables["fpol_c0"]).size - 1)
+
+
+def flux_map(tables, psi0=None, span=None, sqrt_label=False, private=True, flags=None):
+    """(gfhip_flux_map, the array its pointer refers to) from a mapping with efit.nc's dataset names."""
+    first = np.asarray(tables[TABLE_NAMES[0]])
+    if first.ndim != 2:
+        raise ValueError("psi_c00 must be a numr x numz table")
+    coefficients = np.empty((16,) + first.shape, dtype=np.float64)
+    for k, name in enumerate(TABLE_NAMES):
+        table = np.asarray(tables[name], dtype=np.float64)
+        if table.shape != first.shape:
+            raise ValueError("%s has shape %r, psi_c00 %r" % (name, table.shape, first.shape))
+        coefficients[k] = table
+    if psi0 is None or span is None:
+        low, width = default_range(tables)
+        psi0 = low if psi0 is None else psi0
+        span = width if span is None else span
+    if flags is None:
+        flags = (SQRT_LABEL if sqrt_label else 0) | (0 if private else NO_PRIVATE_SUMS)
+    return _Map(float(tables["rmin"]), float(tables["dr"]), float(tables["zmin"]), float(tables["dz"]), first.shape[0],
+                first.shape[1], coefficients.ctypes.data, float(psi0), float(span), int(flags), 0), coefficients
+
+
+def label_host(tables, x, y, z, psi0=None, span=None, sqrt_label=False):
+    """The labels of points on the CPU (gfhip_flux_label_host): the bits of FluxProfile.label, NaN outside the map."""
+    from . import _lib
+    lib = _lib.load()
+    given, keep = flux_map(tables, psi0, span, sqrt_label)
+    columns = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in (x, y, z)]
+    if len({c.size for c in columns}) != 1:
+        raise ValueError("x, y and z differ in length")
+    label = np.empty(columns[0].size, dtype=np.float64)
+    if lib.gfhip_flux_label_host(ctypes.byref(given), *[c.ctypes.data for c in columns], label.size, label.ctypes.data):
+        raise GfHipError(lib.gfhip_last_error(None).decode())
+    del keep
+    return label
+
+
+class FluxProfile:
+    """A radial profile of exact sums on a context's device (gfhip_flux_*, include/gf_hip.h)."""
+
+    def __init__(self, context, tables, edges, psi0=None, span=None, sqrt_label=False, private=True):
+        self.context = context
+        self.lib = context.lib
+        self.tables = tables
+        self.edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        if self.edges.size < 2:
+            raise ValueError("a profile needs at least two edges")
+        self.cells = self.edges.size - 1
+        self.sqrt_label = bool(sqrt_label)
+        self.private = bool(private)
+        given, keep = flux_map(tables, psi0, span, sqrt_label, private)
+        self.psi0, self.span = given.psi0, given.span
+        self.handle = self.lib.gfhip_flux_create(context.handle, ctypes.byref(given), self.edges.ctypes.data, self.cells)
+        del keep                                             # the library has copied the tables
+        if not self.handle:
+            raise GfHipError(self.lib.gfhip_last_error(context.handle).decode())
+
+    def like(self, context):
+        """An empty profile with this one's map, edges and options on another context."""
+        return FluxProfile(context, self.tables, self.edges, self.psi0, self.span, self.sqrt_label, self.private)
+
+    @property
+    def label_kind(self):
+        return "sqrt_s" if self.sqrt_label else "s"
+
+    def add(self, x_key, y_key, z_key, value_key, count):
+        """Bin `count` samples of four fp64 context buffers; asynchronous on the context's stream."""
+        self.context._check(self.lib.gfhip_flux_add(self.handle, key_of(x_key), key_of(y_key), key_of(z_key),
+                                                    key_of(value_key), int(count)))
+
+    def label(self, x_key, y_key, z_key, label_key, count):
+        """The labels of `count` points into the fp64 buffer `label_key` (NaN outside the map); asynchronous."""
+        self.context._check(self.lib.gfhip_flux_label(self.handle, key_of(x_key), key_of(y_key), key_of(z_key),
+                                                      key_of(label_key), int(count)))
+
+    def counts(self):
+        """{samples, outside, skipped}: the samples seen, those off the map or the edges (or with a NaN label) and those
+        inside whose value was NaN or infinite."""
+        values = [ctypes.c_uint64() for _ in range(3)]
+        self.context._check(self.lib.gfhip_flux_counts(self.handle, *[ctypes.byref(v) for v in values]))
+        return dict(zip(("samples", "outside", "skipped"), (v.value for v in values)))
+
+    def state(self):
+        """The canonical limbs, shape (cells, 67): identical bytes for the same samples whatever their route."""
+        limbs = np.empty((self.cells, LIMBS), dtype=np.int64)
+        self.context._check(self.lib.gfhip_flux_state(self.handle, limbs.ctypes.data))
+        return limbs
+
+    def merge(self, limbs, samples=0, outside=0, skipped=0):
+        """Add another profile's state() and counts() (same map and edges: the caller's business)."""
+        limbs = np.ascontiguousarray(limbs, dtype=np.int64)
+        if limbs.ndim != 2 or limbs.shape[1] != LIMBS:
+            raise ValueError("merge: limbs of shape %r are no (cells, %d) state" % (limbs.shape, LIMBS))
+        self.context._check(self.lib.gfhip_flux_merge(self.handle, limbs.ctypes.data, limbs.shape[0], int(samples), int(outside),
+                                                      int(skipped)))
+
+    def read(self, divisor=1.0):
+        """(cells,): the correctly rounded exact sum of each cell, divided by `divisor`."""
+        bins = np.empty(self.cells, dtype=np.float64)
+        self.context._check(self.lib.gfhip_flux_read(self.handle, float(divisor), bins.ctypes.data))
+        return bins
+
+    def info(self):
+        """How deposits are launched: {private_sums, workgroup_size, cap_cells, max_workgroups, lds_bytes}."""
+        info = _Info()
+        self.context._check(self.lib.gfhip_flux_info(self.handle, ctypes.byref(info)))
+        out = {name: int(getattr(info, name)) for name, _ in _Info._fields_}
+        out["private_sums"] = bool(out["private_sums"])
+        return out
+
+    def close(self):
+        if self.handle and self.context.handle:              # a closed context has freed its profiles
+            self.lib.gfhip_flux_destroy(self.handle)
+        self.handle = None
+
+
+def flux_deposition(directory, num_files, tables, cells, low, high, psi0=None, span=None, sqrt_label=False, private=True,
+                    index=0, profile=None):
+    """bin_deposition's counterpart on flux surfaces: d_power of result0.nc .. result<num_files - 1>.nc binned on
+    `cells` uniform cells of the label between `low` and `high`, divided by the total number of rays, written to
+    <directory>/flux_bins.nc.  Returns (bins, counts).  profile: a FluxProfile that receives the exact state as well."""
+    from .backend import Context
+    from . import _lib
+    edges = np.linspace(low, high, cells + 1)
+    context = Context(index)
+    local = FluxProfile(context, tables, edges, psi0, span, sqrt_label, private)
+    names = ("x", "y", "z", "d_power")
+    total = 0
+    for number in range(num_files):
+        file = ResultFile(os.path.join(directory, "result%d.nc" % number))
+        n = file.num_rays
+        total += n
+        keys = ["flux_%s_%d" % (name, n) for name in names]             # one set of buffers per ensemble size
+        for key in keys:
+            context._check(context.lib.gfhip_allocate_buffer(context.handle, key_of(key), n, _lib.GFIR_F64))
+        for record in range(file.records):
+            for name, key in zip(names, keys):
+                context.copy_to_device(key, file.read(name, record))
+            local.add(*keys, n)
+        file.close()
+    bins = local.read(total)
+    counts = local.counts()
+    if profile is not None:
+        profile.merge(local.state(), **counts)
+    psi0, span, kind = local.psi0, local.span, local.label_kind
+    local.close()
+    context.close()
+    write_flux_bins(os.path.join(directory, "flux_bins.nc"), bins, edges, psi0, span, kind, **counts)
+    return bins, counts

@@ -357,6 +357,20 @@ class BinsFile(ResultFile):
         self.lib.H5Aclose(attribute)
         self.lib.H5Sclose(space)
 
+    def float64_attribute(self, name, value):
+        """A global attribute of type NC_DOUBLE."""
+        space = self.lib.H5Screate(_H5S_SCALAR)
+        attribute = self.lib.H5Acreate2(self.file, name.encode(), self.native, space, 0, 0)
+        if attribute < 0:
+            raise IOError("cannot create attribute %s" % name)
+        self.lib.H5Awrite(attribute, self.native, ctypes.byref(ctypes.c_double(float(value))))
+        self.lib.H5Aclose(attribute)
+        self.lib.H5Sclose(space)
+
+    def text_attribute(self, name, text):
+        """A global attribute of type NC_CHAR."""
+        self._string_attribute(self.file, name, text, None)
+
     def close(self):
         if self.file is not None:
             for dataset, _ in self.scales.values():
@@ -379,6 +393,24 @@ def write_bins(path, bins, xbins, ybins, zbins, samples=0, outside=0, skipped=0)
         file.write_variable(name, edges, (dimension,))
     for name, value in (("samples", samples), ("outside", outside), ("skipped", skipped)):
         file.int64_attribute(name, value)
+    file.close()
+
+
+def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside=0, skipped=0):
+    """flux_bins.nc, the radial counterpart of bins.nc: dimensions ns, nsp; f8 variables bins(ns), sbins(nsp), the edges
+    in the label; what became of the samples as global integer attributes; psi0 and span (f8) and the label kind ("s":
+    (psi - psi0)/span, "sqrt_s": its square root) as global attributes."""
+    bins = np.asarray(bins).reshape(-1)
+    file = BinsFile(path)
+    file.create_dimension("ns", bins.size)
+    file.create_dimension("nsp", bins.size + 1)
+    file.write_variable("bins", bins, ("ns",))
+    file.write_variable("sbins", np.asarray(sbins).reshape(-1), ("nsp",))
+    for name, value in (("samples", samples), ("outside", outside), ("skipped", skipped)):
+        file.int64_attribute(name, value)
+    file.float64_attribute("psi0", psi0)
+    file.float64_attribute("span", span)
+    file.text_attribute("label", label)
     file.close()
 
 

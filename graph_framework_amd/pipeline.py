@@ -29,7 +29,7 @@ class OnePass:
     source: the Context that holds the nine trajectory arrays of `num_rays` fp64 elements.
     keys: {file variable (output.RAY_VARIABLES): buffer key in `source`}; the solver's names by default.
     model: "weak_damping" or "root_find" (run_absorption's).  items: GFIR replacing exported workloads, {"weak_damping",
-    "init", "loss", "final", "power"}.  deposition: as in absorption.bin_power.
+    "init", "loss", "final", "power"}.  deposition, flux: as in absorption.bin_power.
     stream: the stream `source` launches on, when the caller knows it: the stage contexts then share it and nothing but
     stream order is needed between the stages; otherwise they get private streams and gfhip_hand_over orders them.
 
@@ -39,7 +39,7 @@ class OnePass:
     root_find synchronises per record in its converge loop, as RootFinder does."""
 
     def __init__(self, source, num_rays, path, model="weak_damping", index=0, stream=None, keys=None, deposition=None,
-                 items=None):
+                 items=None, flux=None):
         items = items or {}
         self.source = source
         self.num_rays = n = int(num_rays)
@@ -56,6 +56,8 @@ class OnePass:
         if deposition is not None:
             from .deposition import Deposition
             self.local = Deposition(self.power.context, *deposition.edges)
+        self.flux = flux
+        self.local_flux = flux.like(self.power.context) if flux is not None else None
 #  The record as the file takes it, on a stream of its own: the copies to the host overlap what `source` does next.
         self.gather = Context(index)
         self.file = ResultFile(path, n)
@@ -89,6 +91,8 @@ class OnePass:
             self.power.run()
         if self.local is not None:
             self.local.add("x", "y", "z", "d_power", self.num_rays)
+        if self.local_flux is not None:
+            self.local_flux.add("x", "y", "z", "d_power", self.num_rays)
         gather = self.gather
         gather.hand_over(self.source, [(self._gathered(name), keys[name]) for name, _ in RAY_VARIABLES])
         gather.hand_over(absorption, [(self._gathered("kamp"), "kamp")])
@@ -101,7 +105,8 @@ class OnePass:
         self.sync.start(write)
 
     def close(self):
-        """Join the writer (its error surfaces here), merge the deposition grid and free the stage contexts."""
+        """Join the writer (its error surfaces here), merge the deposition grid and the flux profile and free the stage
+        contexts."""
         try:
             self.sync.join()
         finally:
@@ -110,5 +115,9 @@ class OnePass:
                 self.deposition.merge(self.local.state(), **self.local.counts())
                 self.local.close()
                 self.local = None
+            if self.local_flux is not None:
+                self.flux.merge(self.local_flux.state(), **self.local_flux.counts())
+                self.local_flux.close()
+                self.local_flux = None
             for context in (self.absorption.context, self.power.context, self.gather):
                 context.close()

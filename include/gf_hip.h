@@ -329,6 +329,66 @@ int gfhip_bins_merge(gfhip_bins *bins, const int64_t *limbs, uint64_t samples, u
 int gfhip_bins_read(gfhip_bins *bins, double divisor, double *values);
 void gfhip_bins_destroy(gfhip_bins *bins);
 
+/* Flux-surface profile: per-sample values binned on the flux label of their position, every cell the EXACT sum
+ * of its samples (the superaccumulator of the deposition grids, state shape (cells, 67)).
+ *
+ * The label (csrc/flux_label.hpp) comes from the EFIT psi spline: the 16 tables psi_c<a><b> (numr x numz,
+ * row-major, table a*4 + b at coefficients + (a*4 + b)*numr*numz) with rmin, dr, zmin, dz, evaluated in the
+ * tracer's own representation, every operation one IEEE fp64 operation in this order, nothing fused:
+ *     R = sqrt(x*x + y*y);  tr = (R - rmin)/dr;  tz = (z - zmin)/dz
+ *     inside the map iff tr >= 0 && tr < numr && tz >= 0 && tz < numz   (a NaN is outside; no clamping)
+ *     i = (int)tr, j = (int)tz, c[a][b] = psi_c<a><b>[i][j]
+ *     col_a = ((c[a][3]*tz + c[a][2])*tz + c[a][1])*tz + c[a][0];  psi = ((col_3*tr + col_2)*tr + col_1)*tr + col_0
+ *     s = (psi - psi0)/span;  label = s, or sqrt(s) with GFHIP_FLUX_SQRT_LABEL (s < 0: NaN, outside)
+ * A sample belongs to cell i iff edges[i] <= label < edges[i+1]; the edges need not be uniform.
+ *
+ * gfhip_flux_create: copies the map (the tables are repacked on the device) and the cells + 1 finite, strictly
+ *   increasing edges.  1 <= cells <= 4096; numr, numz >= 1 and numr*numz <= 2^31; dr, dz, span finite and
+ *   non-zero; rmin, zmin, psi0 finite; no flag bits beyond the two below; reserved = 0.  Up to the cap of
+ *   gfhip_flux_info (256 cells) every workgroup sums its deposits in LDS before they reach memory, unless
+ *   GFHIP_FLUX_NO_PRIVATE_SUMS is set; the state is the same bytes either way.  NULL on failure
+ *   (gfhip_last_error(ctx)).  The profile belongs to the context and is freed with it at the latest.
+ * gfhip_flux_add: as gfhip_bins_add.  `outside`: off the map, off the edges or a NaN label; `skipped`: inside
+ *   with a NaN or infinite value.
+ * gfhip_flux_label: the labels of `count` points into a fourth fp64 buffer, NaN where outside the map.
+ * gfhip_flux_counts / _state / _merge / _read / _destroy: as the deposition grids'; _merge takes the number of
+ *   cells of the incoming state and refuses another shape.
+ * gfhip_flux_info: how the deposits are launched.
+ * gfhip_flux_label_host: no device; flux_label.hpp on the CPU, NaN where outside the map.  Errors:
+ *   gfhip_last_error(NULL). */
+typedef struct gfhip_flux gfhip_flux;
+
+#define GFHIP_FLUX_SQRT_LABEL 1u
+#define GFHIP_FLUX_NO_PRIVATE_SUMS 2u
+
+struct gfhip_flux_map {
+    double rmin, dr, zmin, dz;
+    uint64_t numr, numz;
+    const double *coefficients;
+    double psi0, span;
+    uint32_t flags, reserved;
+};
+
+struct gfhip_flux_info {
+    uint32_t private_sums;       /* 1: deposits are summed in LDS per workgroup */
+    uint32_t workgroup_size;
+    uint64_t cap_cells;          /* the most cells the private path takes */
+    uint64_t max_workgroups;     /* the most workgroups of one launch */
+    uint64_t lds_bytes;          /* dynamic LDS per workgroup */
+};
+
+gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const struct gfhip_flux_map *map, const double *edges, size_t cells);
+int gfhip_flux_add(gfhip_flux *flux, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count);
+int gfhip_flux_label(gfhip_flux *flux, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t label_key, size_t count);
+int gfhip_flux_counts(gfhip_flux *flux, uint64_t *samples, uint64_t *outside, uint64_t *skipped);
+int gfhip_flux_state(gfhip_flux *flux, int64_t *limbs);
+int gfhip_flux_merge(gfhip_flux *flux, const int64_t *limbs, size_t cells, uint64_t samples, uint64_t outside, uint64_t skipped);
+int gfhip_flux_read(gfhip_flux *flux, double divisor, double *values);
+int gfhip_flux_info(gfhip_flux *flux, struct gfhip_flux_info *info);
+void gfhip_flux_destroy(gfhip_flux *flux);
+int gfhip_flux_label_host(const struct gfhip_flux_map *map, const double *x, const double *y, const double *z,
+                          size_t count, double *label);
+
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
  * Non-zero for a NaN or an infinity among the values (gfhip_last_error(NULL)). */
