@@ -165,12 +165,8 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
     for name in ("x", "y", "z"):                                            # dataset.read(file, 0) ... :767-771
         host[name][:] = file.read(name, 0)
         host[name + "_last"][:] = host[name]
-    grids = []                                                              # (the caller's, its local twin on this context)
-    if deposition is not None:
-        from .deposition import Deposition
-        grids.append((deposition, Deposition(work.context, *deposition.edges)))
-    if flux is not None:
-        grids.append((flux, flux.like(work.context)))
+#  (the caller's, its local twin on this context)
+    grids = [(target, target.like(work.context)) for target in (deposition, flux) if target is not None]
     if grids:
         for name in ("x", "y", "z"):
             work.copy_to_device(name, host[name])

@@ -1,0 +1,38 @@
+//------------------------------------------------------------------------------
+///  @file cell_launch.hpp
+///  @brief What gf_hip.cpp launches of deposition.hip and flux_profile.hip.
+//------------------------------------------------------------------------------
+#ifndef GFHIP_CELL_LAUNCH_HPP
+#define GFHIP_CELL_LAUNCH_HPP
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include "flux_label.hpp"
+
+namespace gfhip {
+
+//  deposition.hip.  A store of exact sums, cells x 67 limbs: canonical in place, rounded and divided into `values`,
+//  and `words` limbs (or counters) of another one added in.
+void launch_cells_normalise(void *state, const size_t cells, hipStream_t stream);
+void launch_cells_round(const void *state, const size_t cells, const double divisor, double *values, hipStream_t stream);
+void launch_cells_merge(void *state, const void *other, const size_t words, hipStream_t stream);
+//  The deposits of a 3-D grid.  edges: the three axes' one after the other; scale: n/(last edge - first edge) per axis.
+void launch_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
+                    const double *edges, const int nx, const int ny, const int nz, const double *scale,
+                    void *state, unsigned long long *counters, const unsigned int num_cus, hipStream_t stream);
+
+//  flux_profile.hip.  The shape of a profile's deposit launches, decided once per profile.
+void flux_launch_shape(const size_t cells, const bool allow_private, const unsigned int num_cus,
+                       bool *is_private, size_t *cap, unsigned int *block, size_t *max_workgroups, size_t *lds_bytes);
+hipError_t flux_prepare();
+void launch_flux_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
+                         const flux::map &m, const double *packed, const double *edges, const size_t cells, const double scale,
+                         const bool is_private, const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                         void *state, unsigned long long *counters, hipStream_t stream);
+void launch_flux_label(const double *x, const double *y, const double *z, const size_t count, const flux::map &m,
+                       const double *packed, double *label, hipStream_t stream);
+
+}  // namespace gfhip
+
+#endif

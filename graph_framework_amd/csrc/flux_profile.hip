@@ -4,7 +4,7 @@
 ///
 ///  A sample (x, y, z, value) gets the flux label of flux_label.hpp from the repacked psi tables ([cell][16]: a
 ///  lane's 16 coefficients are one 128-byte line, read with 16-byte loads) and belongs to profile cell i iff
-///  edge[i] <= label < edge[i+1] (deposition.hip's rule).  Every profile cell is the superaccumulator of
+///  edge[i] <= label < edge[i+1] (cell_deposit.hpp's find_cell, deposition.hip's rule).  Every profile cell is the superaccumulator of
 ///  superacc.hpp, 67 limbs of 64 bits.
 ///
 ///  Private path: every workgroup owns a grid of cells x 67 limbs in LDS (536 B per cell: 256 cells are 134 KiB of the
@@ -15,11 +15,14 @@
 ///  deposits of one launch, so the 2^30 rule of superacc.hpp holds as the host applies it to whole launches.
 ///
 ///  Global path (more cells than the cap, or flag bit 1 of the map): deposits go to the global state as in
-///  deposition.hip's deposit_kernel.
+///  deposition.hip's deposit_kernel.  What a sample adds, the counters, the wave-level pre-sum and the atomic adds are
+///  the functions of cell_deposit.hpp in both kernels; this one has the label and the private grid of its own.
 //------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cell_deposit.hpp"
+#include "cell_launch.hpp"
 #include "flux_label.hpp"
 #include "superacc.hpp"
 
@@ -33,32 +36,6 @@ constexpr size_t lds_per_workgroup = 160u*1024u;
 constexpr size_t private_cap = 256;                    // cells: 256*536 + 257*8 = 139,272 B of the 163,840 a workgroup may declare
 constexpr size_t private_cap_bytes = private_cap*superacc::limbs*sizeof(unsigned long long) + (private_cap + 1)*sizeof(double);
 static_assert(private_cap_bytes <= lds_per_workgroup, "the cap fits one workgroup's LDS");
-
-//  The cell of `c` among the n + 1 increasing edges `e` (LDS), or -1: outside [e[0], e[n]) or NaN.  deposition.hip's
-//  find_cell: the guess from the uniform spacing is right or off by one for linspace edges; the stored edges decide.
-__device__ __forceinline__ int find_cell(const double *e, const int n, const double scale, const double c) {
-    if (!(c >= e[0] && c < e[n])) return -1;
-    const double t = (c - e[0])*scale;
-    int g = t >= 0.0 && t < static_cast<double> (n) ? static_cast<int> (t) : 0;
-    if (c >= e[g] && c < e[g + 1]) return g;
-    if (g + 1 < n && c >= e[g + 1] && c < e[g + 2]) return g + 1;
-    if (g > 0 && c >= e[g - 1] && c < e[g]) return g - 1;
-    int low = 0, high = n;                             // e[low] <= c < e[high]
-    while (high - low > 1) {
-        const int middle = (low + high)/2;
-        if (c >= e[middle]) {
-            low = middle;
-        } else {
-            high = middle;
-        }
-    }
-    return low;
-}
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-    for (int offset = 32; offset > 0; offset >>= 1) v += __shfl_xor(v, offset, 64);
-    return v;
-}
 
 //  The label of one point, NaN outside the map.  `packed`: [table cell][16], 16-byte aligned.
 __device__ __forceinline__ double label_at(const flux::map &m, const double *__restrict__ packed,
@@ -95,61 +72,27 @@ flux_deposit_kernel(const double *__restrict__ x, const double *__restrict__ y, 
     for (int i = threadIdx.x; i <= cells; i += blockDim.x) staged[i] = edges[i];
     __syncthreads();
 
-    unsigned long long seen = 0, outside = 0, skipped = 0;                      // wave-uniform
+    deposit::tallies tally;
     const unsigned long long stride = static_cast<unsigned long long> (gridDim.x)*blockDim.x;
 //  `base` is the same for every lane of the workgroup: the ballots and shuffles below are executed by whole waves, and
 //  every wave of the workgroup arrives at the barrier before the flush.
     for (unsigned long long base = static_cast<unsigned long long> (blockIdx.x)*blockDim.x; base < count; base += stride) {
         const unsigned long long at = base + threadIdx.x;
         const bool present = at < count;
-        bool inside = false, finite = false;
-        unsigned int key = 0;                          // cell*64 + first limb
-        long long c0 = 0, c1 = 0, c2 = 0;
+        int cell = -1;                                 // outside, as in the lanes past the end
+        double v = 0.0;
         if (present) {
-            const double v = value[at];
-            const int cell = find_cell(staged, cells, scale, label_at(m, packed, x[at], y[at], z[at]));
-            inside = cell >= 0;
-            finite = superacc::is_finite(v);
-            if (inside && finite) {
-                const superacc::pieces p = superacc::split(v);
-                key = static_cast<unsigned int> (cell)*64u + static_cast<unsigned int> (p.first);
-                c0 = p.negative ? -static_cast<long long> (p.chunk[0]) : static_cast<long long> (p.chunk[0]);
-                c1 = p.negative ? -static_cast<long long> (p.chunk[1]) : static_cast<long long> (p.chunk[1]);
-                c2 = p.negative ? -static_cast<long long> (p.chunk[2]) : static_cast<long long> (p.chunk[2]);
-            }
+            v = value[at];
+            cell = deposit::find_cell(staged, cells, scale, label_at(m, packed, x[at], y[at], z[at]));
         }
-        seen += __popcll(__ballot(present));
-        outside += __popcll(__ballot(present && !inside));
-        skipped += __popcll(__ballot(present && inside && !finite));
-
-        bool adds = (c0 | c1 | c2) != 0;               // a zero adds nothing
-        if constexpr (!PRIVATE) {
-//  Global path, as deposit_kernel: when every adding lane has the same cell and the same first limb (identical rays), sum
-//  the chunks over the wave, three atomics from one lane.  Exact: the limbs are integers.  The private path does without:
-//  measured with and without it, it made no difference there.
-            const unsigned long long adders = __ballot(adds);
-            if (adders == 0) continue;                 // wave-uniform
-            const unsigned int first = __builtin_amdgcn_readlane(key, __ffsll(static_cast<long long> (adders)) - 1);
-            if (__ballot(adds && key != first) == 0) {
-                c0 = wave_sum(c0);
-                c1 = wave_sum(c1);
-                c2 = wave_sum(c2);
-                key = first;
-                adds = (threadIdx.x & 63u) == 0;
-            }
-        }
-        if (adds) {
-            const size_t limb = static_cast<size_t> (key >> 6)*superacc::limbs + (key & 63u);
-//  The results are unused: no-return atomics, ds_add_u64 on the private grid and global_atomic_add_x2 on the state.
-            if constexpr (PRIVATE) {
-                if (c0) atomicAdd(&shared[limb], static_cast<unsigned long long> (c0));
-                if (c1) atomicAdd(&shared[limb + 1], static_cast<unsigned long long> (c1));
-                if (c2) atomicAdd(&shared[limb + 2], static_cast<unsigned long long> (c2));
-            } else {
-                if (c0) atomicAdd(state + limb, static_cast<unsigned long long> (c0));
-                if (c1) atomicAdd(state + limb + 1, static_cast<unsigned long long> (c1));
-                if (c2) atomicAdd(state + limb + 2, static_cast<unsigned long long> (c2));
-            }
+        const deposit::contribution a = deposit::contribution_of(cell >= 0, static_cast<unsigned int> (cell), v);
+        deposit::count(tally, present, a);
+//  The private grid takes every lane's chunks as they are (ds_add_u64): the pre-sum of the global path, measured with
+//  and without it, made no difference there.
+        if constexpr (PRIVATE) {
+            deposit::add_limbs(shared, a.key, a.c0, a.c1, a.c2);
+        } else {
+            deposit::add_limbs_presummed(state, a);
         }
     }
     if constexpr (PRIVATE) {
@@ -159,11 +102,7 @@ flux_deposit_kernel(const double *__restrict__ x, const double *__restrict__ y, 
             if (sum) atomicAdd(state + i, sum);
         }
     }
-    if ((threadIdx.x & 63u) == 0) {
-        if (seen) atomicAdd(counters, seen);
-        if (outside) atomicAdd(counters + 1, outside);
-        if (skipped) atomicAdd(counters + 2, skipped);
-    }
+    deposit::flush(tally, counters);
 }
 
 //  One lane per point: its label, NaN outside the map.

@@ -33,6 +33,7 @@
 #include "../../include/gf_hip.h"
 #include "plan.hpp"
 
+#include "cell_launch.hpp"
 #include "converge_state.hpp"
 #include "flux_label.hpp"
 #include "hand_over.hpp"
@@ -44,23 +45,6 @@ void launch_max_reduce(const void *in, const size_t n, const bool f64,
 void launch_converge_decide(const bool f64, unsigned long long *reduced, void *state, hipStream_t stream);
 void launch_converge_decide_batch(const bool f64, unsigned long long *reduced, void *state, const unsigned int count, hipStream_t stream);
 void launch_max_modulus(const void *in, const size_t n, const bool f64, void *result, hipStream_t stream);
-//  deposition.hip
-void launch_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
-                    const double *edges, const int nx, const int ny, const int nz, const double *scale,
-                    void *state, unsigned long long *counters, const unsigned int num_cus, hipStream_t stream);
-void launch_bins_normalise(void *state, const size_t cells, hipStream_t stream);
-void launch_bins_round(const void *state, const size_t cells, const double divisor, double *bins, hipStream_t stream);
-void launch_bins_merge(void *state, const void *other, const size_t words, hipStream_t stream);
-//  flux_profile.hip
-void flux_launch_shape(const size_t cells, const bool allow_private, const unsigned int num_cus,
-                       bool *is_private, size_t *cap, unsigned int *block, size_t *max_workgroups, size_t *lds_bytes);
-hipError_t flux_prepare();
-void launch_flux_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
-                         const flux::map &m, const double *packed, const double *edges, const size_t cells, const double scale,
-                         const bool is_private, const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
-                         void *state, unsigned long long *counters, hipStream_t stream);
-void launch_flux_label(const double *x, const double *y, const double *z, const size_t count, const flux::map &m,
-                       const double *packed, double *label, hipStream_t stream);
 }
 
 namespace {
@@ -217,30 +201,37 @@ struct gfhip_kernel {
     std::vector<double> samples;                   // durations drained by the last gfhip_kernel_timing
 };
 
-//  A 3-D deposition grid: per cell the 67 limbs of superacc.hpp, [cell][limb].
-struct gfhip_bins {
+//  A store of exact sums, what a deposition grid and a flux profile both are: per cell the 67 limbs of superacc.hpp,
+//  [cell][limb], and what became of the samples.  The entry points check their own arguments and call these.
+struct exact_cells {
     gfhip_context *ctx = nullptr;
-    int n[3] = {0, 0, 0};
     size_t cells = 0;
-    double scale[3] = {0.0, 0.0, 0.0};                 // n/(last edge - first edge): the kernel's first guess of a cell
-    device_ptr<double> edges;                          // the three axes' edges one after the other
     device_ptr<> state;
     device_ptr<unsigned long long> counters;           // samples, outside, skipped
-    device_ptr<double> rounded;                        // what gfhip_bins_read copies out (allocated by the first read)
+    device_ptr<double> rounded;                        // what read() copies out (allocated by the first read)
     uint64_t pending = 0;                              // deposits since the state was last canonical
+
+    int create(gfhip_context *context, size_t count);  // allocated and zero
+    int normalise();
+    template<typename LAUNCH> int add(size_t count, LAUNCH launch);
+    int counts(uint64_t *samples, uint64_t *outside, uint64_t *skipped);
+    int state_to(int64_t *limbs);
+    int merge(const int64_t *limbs, uint64_t samples, uint64_t outside, uint64_t skipped);
+    int read(double divisor, double *values);
 };
 
-//  A flux-surface profile: per cell the 67 limbs of superacc.hpp, [cell][limb]; the psi tables as [table cell][16].
-struct gfhip_flux {
-    gfhip_context *ctx = nullptr;
+//  A 3-D deposition grid.
+struct gfhip_bins : exact_cells {
+    int n[3] = {0, 0, 0};
+    double scale[3] = {0.0, 0.0, 0.0};                 // n/(last edge - first edge): the kernel's first guess of a cell
+    device_ptr<double> edges;                          // the three axes' edges one after the other
+};
+
+//  A flux-surface profile; the psi tables as [table cell][16].
+struct gfhip_flux : exact_cells {
     gfhip::flux::map map = {};
-    size_t cells = 0;
     double scale = 0.0;                                // cells/(last edge - first edge)
     device_ptr<double> packed, edges;
-    device_ptr<> state;
-    device_ptr<unsigned long long> counters;           // samples, outside, skipped
-    device_ptr<double> rounded;
-    uint64_t pending = 0;                              // deposits since the state was last canonical
     bool is_private = false;
     size_t cap = 0, max_workgroups = 0, lds_bytes = 0;
     unsigned int block = 0;
@@ -1556,7 +1547,127 @@ extern "C" int gfhip_kernel_timing_samples(gfhip_kernel *k, double *ms, size_t c
     return 0;
 }
 
-//  Deposition grids (deposition.hip, superacc.hpp).  The limits of a grid: at most 2047 cells per axis, so that the
+//  Stores of exact sums (cell_launch.hpp, superacc.hpp): what deposition grids and flux profiles share.
+int exact_cells::create(gfhip_context *context, const size_t count) {
+    ctx = context;
+    cells = count;
+    const size_t bytes = cells*gfhip::superacc::limbs*sizeof(int64_t);
+    return ctx->check(allocate(state, bytes), "hipMalloc(cells)") ||
+           ctx->check(hipMemset(state.get(), 0, bytes), "hipMemset(cells)") ||
+           ctx->check(allocate(counters, 3*sizeof(unsigned long long)), "hipMalloc(counters)") ||
+           ctx->check(hipMemset(counters.get(), 0, 3*sizeof(unsigned long long)), "hipMemset(counters)");
+}
+
+//  The state canonical in place: before the deposits since the last time could reach 2^30 (a limb takes 2^31),
+//  before the state is handed out and before it is rounded.  Later deposits add to the canonical digits.
+int exact_cells::normalise() {
+    gfhip::launch_cells_normalise(state.get(), cells, ctx->stream);
+    pending = 0;
+    return ctx->check(hipGetLastError(), "normalise launch");
+}
+
+//  `count` deposits, `launch(first, piece)` enqueueing those of the samples first .. first + piece: at most 2^30
+//  between two normalisations (superacc.hpp); a workgroup-private limb sees fewer than its launch.
+template<typename LAUNCH>
+int exact_cells::add(const size_t count, LAUNCH launch) {
+    if (enter(ctx)) return 1;
+    for (size_t first = 0; first < count;) {
+        const size_t piece = std::min<size_t> (count - first, gfhip::superacc::deposits_per_normalise);
+        if (pending + piece > gfhip::superacc::deposits_per_normalise && normalise()) return 1;
+        launch(first, piece);
+        GFHIP_TRY(ctx, hipGetLastError(), "deposit launch");
+        pending += piece;
+        first += piece;
+    }
+    return 0;
+}
+
+int exact_cells::counts(uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
+    if (enter(ctx)) return 1;
+    unsigned long long host[3] = {0, 0, 0};
+    GFHIP_TRY(ctx, hipMemcpyAsync(host, counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (samples) *samples = host[0];
+    if (outside) *outside = host[1];
+    if (skipped) *skipped = host[2];
+    return 0;
+}
+
+int exact_cells::state_to(int64_t *limbs) {
+    if (enter(ctx) || normalise()) return 1;
+    GFHIP_TRY(ctx, hipMemcpyAsync(limbs, state.get(), cells*gfhip::superacc::limbs*sizeof(int64_t), hipMemcpyDeviceToHost,
+                                  ctx->stream), "hipMemcpyAsync(cells)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+int exact_cells::merge(const int64_t *limbs, const uint64_t samples, const uint64_t outside, const uint64_t skipped) {
+    if (enter(ctx)) return 1;
+    const size_t words = cells*gfhip::superacc::limbs;
+    const unsigned long long incoming[3] = {samples, outside, skipped};
+    device_ptr<> other;                                // the incoming limbs, then the three counts
+    GFHIP_TRY(ctx, allocate(other, (words + 3)*sizeof(int64_t)), "hipMalloc(merge)");
+    char *counts_at = static_cast<char *> (other.get()) + words*sizeof(int64_t);
+    GFHIP_TRY(ctx, hipMemcpyAsync(other.get(), limbs, words*sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
+    GFHIP_TRY(ctx, hipMemcpyAsync(counts_at, incoming, sizeof(incoming), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
+//  Canonical digits (below 2^32) on top of a state that 2^30 deposits may have reached: still inside a limb.
+    gfhip::launch_cells_merge(state.get(), other.get(), words, ctx->stream);
+    gfhip::launch_cells_merge(counters.get(), counts_at, 3, ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "merge launch");
+    if (normalise()) return 1;
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // `other` is freed on return
+    return 0;
+}
+
+int exact_cells::read(const double divisor, double *values) {
+    if (enter(ctx)) return 1;
+    if (!rounded) GFHIP_TRY(ctx, allocate(rounded, cells*sizeof(double)), "hipMalloc(rounded cells)");
+    if (normalise()) return 1;
+    gfhip::launch_cells_round(state.get(), cells, divisor, rounded.get(), ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "round launch");
+    GFHIP_TRY(ctx, hipMemcpyAsync(values, rounded.get(), cells*sizeof(double), hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpyAsync(rounded cells)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+//  Whether the n + 1 edges of an axis are finite and strictly increasing.
+static bool edges_increase(const double *edges, const size_t n) {
+    for (size_t i = 0; i <= n; i++) {
+        if (!std::isfinite(edges[i]) || (i && !(edges[i - 1] < edges[i]))) return false;
+    }
+    return true;
+}
+
+//  Four fp64 buffers of at least `count` elements, or the message about `noun`; nothing is enqueued.
+static int fp64_columns(gfhip_context *ctx, const char *noun, const uint64_t (&keys)[4], const size_t count, double **columns) {
+    for (int c = 0; c < 4; c++) {
+        const buffer *found = find_buffer(ctx, keys[c]);
+        if (!found) return 1;
+        if (found->dtype != GFIR_F64) return ctx->fail(std::string(noun) + " takes fp64 buffers");
+        if (found->count < count) return ctx->fail(std::string(noun) + " buffer is shorter than the sample count");
+        columns[c] = static_cast<double *> (found->pointer);
+    }
+    return 0;
+}
+
+//  gfhip_*_destroy: behind everything the context has queued, out of the context's list.
+template<typename T>
+static void destroy_in(std::vector<std::unique_ptr<T>> gfhip_context::*list, T *object) {
+    if (!object) return;
+    gfhip_context *ctx = object->ctx;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    auto &owned = ctx->*list;
+    for (auto it = owned.begin(); it != owned.end(); ++it) {
+        if (it->get() == object) {
+            owned.erase(it);
+            return;
+        }
+    }
+}
+
+//  Deposition grids (deposition.hip).  The limits of a grid: at most 2047 cells per axis, so that the
 //  three axes' edges (3 x 2048 doubles, 48 KiB) fit the LDS a workgroup gets without asking; at most 2^25 cells
 //  (536 B each: 16.8 GiB of state), so that cell*64 + limb fits the 32-bit key the deposit kernel compares.
 static const size_t bins_axis_limit = 2047, bins_cell_limit = static_cast<size_t> (1) << 25;
@@ -1573,11 +1684,9 @@ extern "C" gfhip_bins *gfhip_bins_create(gfhip_context *ctx, const double *xedge
             ctx->fail("a deposition grid has 1 to 2047 cells per axis");
             return nullptr;
         }
-        for (size_t i = 0; i <= n[a]; i++) {
-            if (!std::isfinite(axes[a][i]) || (i && !(axes[a][i - 1] < axes[a][i]))) {
-                ctx->fail("the edges of a deposition grid must be finite and strictly increasing");
-                return nullptr;
-            }
+        if (!edges_increase(axes[a], n[a])) {
+            ctx->fail("the edges of a deposition grid must be finite and strictly increasing");
+            return nullptr;
         }
         edges.insert(edges.end(), axes[a], axes[a] + n[a] + 1);
         cells *= n[a];
@@ -1588,19 +1697,13 @@ extern "C" gfhip_bins *gfhip_bins_create(gfhip_context *ctx, const double *xedge
     }
     if (ctx->check(hipSetDevice(ctx->device), "hipSetDevice")) return nullptr;
     std::unique_ptr<gfhip_bins> b(new gfhip_bins);
-    b->ctx = ctx;
-    b->cells = cells;
     for (int a = 0; a < 3; a++) {
         b->n[a] = static_cast<int> (n[a]);
         b->scale[a] = static_cast<double> (n[a])/(axes[a][n[a]] - axes[a][0]);
     }
-    const size_t bytes = cells*gfhip::superacc::limbs*sizeof(int64_t);
     if (ctx->check(allocate(b->edges, edges.size()*sizeof(double)), "hipMalloc(edges)") ||
         ctx->check(hipMemcpy(b->edges.get(), edges.data(), edges.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
-        ctx->check(allocate(b->state, bytes), "hipMalloc(bins)") ||
-        ctx->check(hipMemset(b->state.get(), 0, bytes), "hipMemset(bins)") ||
-        ctx->check(allocate(b->counters, 3*sizeof(unsigned long long)), "hipMalloc(counters)") ||
-        ctx->check(hipMemset(b->counters.get(), 0, 3*sizeof(unsigned long long)), "hipMemset(counters)")) {
+        b->create(ctx, cells)) {
         return nullptr;
     }
     ctx->bins.push_back(std::move(b));
@@ -1608,108 +1711,40 @@ extern "C" gfhip_bins *gfhip_bins_create(gfhip_context *ctx, const double *xedge
 }
 
 extern "C" void gfhip_bins_destroy(gfhip_bins *b) {
-    if (!b) return;
-    gfhip_context *ctx = b->ctx;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto it = ctx->bins.begin(); it != ctx->bins.end(); ++it) {
-        if (it->get() == b) {
-            ctx->bins.erase(it);
-            return;
-        }
-    }
-}
-
-//  The state canonical in place: before the deposits since the last time could reach 2^30 (a limb takes 2^31),
-//  before the state is handed out and before it is rounded.  Later deposits add to the canonical digits.
-static int bins_normalise(gfhip_bins *b) {
-    gfhip::launch_bins_normalise(b->state.get(), b->cells, b->ctx->stream);
-    b->pending = 0;
-    return b->ctx->check(hipGetLastError(), "normalise launch");
+    destroy_in(&gfhip_context::bins, b);
 }
 
 extern "C" int gfhip_bins_add(gfhip_bins *b, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count) {
     if (!b) return 1;
-    gfhip_context *ctx = b->ctx;
-//  Misuse is reported before anything is enqueued.
-    const uint64_t keys[4] = {x_key, y_key, z_key, value_key};
-    const double *columns[4];
-    for (int c = 0; c < 4; c++) {
-        const buffer *found = find_buffer(ctx, keys[c]);
-        if (!found) return 1;
-        if (found->dtype != GFIR_F64) return ctx->fail("deposition reads fp64 buffers");
-        if (found->count < count) return ctx->fail("a deposition buffer is shorter than the sample count");
-        columns[c] = static_cast<const double *> (found->pointer);
-    }
-    if (enter(ctx)) return 1;
-    for (size_t first = 0; first < count;) {
-        const size_t piece = std::min<size_t> (count - first, gfhip::superacc::deposits_per_normalise);
-        if (b->pending + piece > gfhip::superacc::deposits_per_normalise && bins_normalise(b)) return 1;
+    double *columns[4];
+    if (fp64_columns(b->ctx, "a deposition grid", {x_key, y_key, z_key, value_key}, count, columns)) return 1;
+    return b->add(count, [&](const size_t first, const size_t piece) {
         gfhip::launch_deposit(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
                               b->edges.get(), b->n[0], b->n[1], b->n[2], b->scale, b->state.get(), b->counters.get(),
-                              ctx->num_cus, ctx->stream);
-        GFHIP_TRY(ctx, hipGetLastError(), "deposit launch");
-        b->pending += piece;
-        first += piece;
-    }
-    return 0;
+                              b->ctx->num_cus, b->ctx->stream);
+    });
 }
 
 extern "C" int gfhip_bins_counts(gfhip_bins *b, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    if (!b) return 1;
-    gfhip_context *ctx = b->ctx;
-    if (enter(ctx)) return 1;
-    unsigned long long host[3] = {0, 0, 0};
-    GFHIP_TRY(ctx, hipMemcpyAsync(host, b->counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    if (samples) *samples = host[0];
-    if (outside) *outside = host[1];
-    if (skipped) *skipped = host[2];
-    return 0;
+    return b ? b->counts(samples, outside, skipped) : 1;
 }
 
 extern "C" int gfhip_bins_state(gfhip_bins *b, int64_t *limbs) {
-    if (!b || !limbs) return 1;
-    gfhip_context *ctx = b->ctx;
-    if (enter(ctx) || bins_normalise(b)) return 1;
-    GFHIP_TRY(ctx, hipMemcpyAsync(limbs, b->state.get(), b->cells*gfhip::superacc::limbs*sizeof(int64_t), hipMemcpyDeviceToHost,
-                                  ctx->stream), "hipMemcpyAsync(bins)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return 0;
+    if (!b) return 1;
+    if (!limbs) return b->ctx->fail("gfhip_bins_state needs a destination");
+    return b->state_to(limbs);
 }
 
 extern "C" int gfhip_bins_merge(gfhip_bins *b, const int64_t *limbs, uint64_t samples, uint64_t outside, uint64_t skipped) {
-    if (!b || !limbs) return 1;
-    gfhip_context *ctx = b->ctx;
-    if (enter(ctx)) return 1;
-    const size_t words = b->cells*gfhip::superacc::limbs;
-    const unsigned long long counts[3] = {samples, outside, skipped};
-    device_ptr<> other;                                // the incoming limbs, then the three counts
-    GFHIP_TRY(ctx, allocate(other, (words + 3)*sizeof(int64_t)), "hipMalloc(merge)");
-    char *counts_at = static_cast<char *> (other.get()) + words*sizeof(int64_t);
-    GFHIP_TRY(ctx, hipMemcpyAsync(other.get(), limbs, words*sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
-    GFHIP_TRY(ctx, hipMemcpyAsync(counts_at, counts, sizeof(counts), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
-//  Canonical digits (below 2^32) on top of a state that 2^30 deposits may have reached: still inside a limb.
-    gfhip::launch_bins_merge(b->state.get(), other.get(), words, ctx->stream);
-    gfhip::launch_bins_merge(b->counters.get(), counts_at, 3, ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "merge launch");
-    if (bins_normalise(b)) return 1;
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // `other` is freed on return
-    return 0;
+    if (!b) return 1;
+    if (!limbs) return b->ctx->fail("gfhip_bins_merge needs a state");
+    return b->merge(limbs, samples, outside, skipped);
 }
 
 extern "C" int gfhip_bins_read(gfhip_bins *b, double divisor, double *bins) {
-    if (!b || !bins) return 1;
-    gfhip_context *ctx = b->ctx;
-    if (enter(ctx)) return 1;
-    if (!b->rounded) GFHIP_TRY(ctx, allocate(b->rounded, b->cells*sizeof(double)), "hipMalloc(rounded bins)");
-    if (bins_normalise(b)) return 1;
-    gfhip::launch_bins_round(b->state.get(), b->cells, divisor, b->rounded.get(), ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "round launch");
-    GFHIP_TRY(ctx, hipMemcpyAsync(bins, b->rounded.get(), b->cells*sizeof(double), hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpyAsync(rounded bins)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return 0;
+    if (!b) return 1;
+    if (!bins) return b->ctx->fail("gfhip_bins_read needs a destination");
+    return b->read(divisor, bins);
 }
 
 //  Flux profiles (flux_profile.hip, flux_label.hpp).  At most 4096 cells: the edges are staged in LDS on both paths.
@@ -1755,11 +1790,9 @@ extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_ma
         ctx->fail("a flux profile has 1 to 4096 cells");
         return nullptr;
     }
-    for (size_t i = 0; i <= cells; i++) {
-        if (!std::isfinite(edges[i]) || (i && !(edges[i - 1] < edges[i]))) {
-            ctx->fail("the edges of a flux profile must be finite and strictly increasing");
-            return nullptr;
-        }
+    if (!edges_increase(edges, cells)) {
+        ctx->fail("the edges of a flux profile must be finite and strictly increasing");
+        return nullptr;
     }
     std::unique_ptr<gfhip_flux> f(new gfhip_flux);
     if (const char *refused = flux_map_of(map, f->map)) {
@@ -1767,8 +1800,6 @@ extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_ma
         return nullptr;
     }
     if (ctx->check(hipSetDevice(ctx->device), "hipSetDevice")) return nullptr;
-    f->ctx = ctx;
-    f->cells = cells;
     f->scale = static_cast<double> (cells)/(edges[cells] - edges[0]);
     gfhip::flux_launch_shape(cells, !(map->flags & gfhip::flux::flag_no_private_sums), ctx->num_cus, &f->is_private, &f->cap,
                              &f->block, &f->max_workgroups, &f->lds_bytes);
@@ -1785,15 +1816,11 @@ extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_ma
         const double *from = map->coefficients + k*table;
         for (size_t at = 0; at < table; at++) packed[at*16 + k] = from[at];
     }
-    const size_t bytes = cells*gfhip::superacc::limbs*sizeof(int64_t);
     if (ctx->check(allocate(f->packed, packed.size()*sizeof(double)), "hipMalloc(flux tables)") ||
         ctx->check(hipMemcpy(f->packed.get(), packed.data(), packed.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
         ctx->check(allocate(f->edges, (cells + 1)*sizeof(double)), "hipMalloc(edges)") ||
         ctx->check(hipMemcpy(f->edges.get(), edges, (cells + 1)*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
-        ctx->check(allocate(f->state, bytes), "hipMalloc(flux profile)") ||
-        ctx->check(hipMemset(f->state.get(), 0, bytes), "hipMemset(flux profile)") ||
-        ctx->check(allocate(f->counters, 3*sizeof(unsigned long long)), "hipMalloc(counters)") ||
-        ctx->check(hipMemset(f->counters.get(), 0, 3*sizeof(unsigned long long)), "hipMemset(counters)") ||
+        f->create(ctx, cells) ||
         (f->is_private && ctx->check(gfhip::flux_prepare(), "hipFuncSetAttribute(flux deposit)"))) {
         return nullptr;
     }
@@ -1802,63 +1829,25 @@ extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_ma
 }
 
 extern "C" void gfhip_flux_destroy(gfhip_flux *f) {
-    if (!f) return;
-    gfhip_context *ctx = f->ctx;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto it = ctx->fluxes.begin(); it != ctx->fluxes.end(); ++it) {
-        if (it->get() == f) {
-            ctx->fluxes.erase(it);
-            return;
-        }
-    }
-}
-
-static int flux_normalise(gfhip_flux *f) {
-    gfhip::launch_bins_normalise(f->state.get(), f->cells, f->ctx->stream);
-    f->pending = 0;
-    return f->ctx->check(hipGetLastError(), "normalise launch");
-}
-
-//  Four fp64 buffers of at least `count` elements, or the message; nothing is enqueued.
-static int flux_columns(gfhip_context *ctx, const uint64_t *keys, const size_t count, double **columns) {
-    for (int c = 0; c < 4; c++) {
-        const buffer *found = find_buffer(ctx, keys[c]);
-        if (!found) return 1;
-        if (found->dtype != GFIR_F64) return ctx->fail("a flux profile reads and writes fp64 buffers");
-        if (found->count < count) return ctx->fail("a flux profile buffer is shorter than the sample count");
-        columns[c] = static_cast<double *> (found->pointer);
-    }
-    return 0;
+    destroy_in(&gfhip_context::fluxes, f);
 }
 
 extern "C" int gfhip_flux_add(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count) {
     if (!f) return 1;
-    gfhip_context *ctx = f->ctx;
-    const uint64_t keys[4] = {x_key, y_key, z_key, value_key};
     double *columns[4];
-    if (flux_columns(ctx, keys, count, columns)) return 1;
-    if (enter(ctx)) return 1;
-//  At most 2^30 deposits between two normalisations (superacc.hpp); a private limb sees fewer than its launch.
-    for (size_t first = 0; first < count;) {
-        const size_t piece = std::min<size_t> (count - first, gfhip::superacc::deposits_per_normalise);
-        if (f->pending + piece > gfhip::superacc::deposits_per_normalise && flux_normalise(f)) return 1;
+    if (fp64_columns(f->ctx, "a flux profile", {x_key, y_key, z_key, value_key}, count, columns)) return 1;
+    return f->add(count, [&](const size_t first, const size_t piece) {
         gfhip::launch_flux_deposit(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
                                    f->map, f->packed.get(), f->edges.get(), f->cells, f->scale, f->is_private, f->block,
-                                   f->max_workgroups, f->lds_bytes, f->state.get(), f->counters.get(), ctx->stream);
-        GFHIP_TRY(ctx, hipGetLastError(), "flux deposit launch");
-        f->pending += piece;
-        first += piece;
-    }
-    return 0;
+                                   f->max_workgroups, f->lds_bytes, f->state.get(), f->counters.get(), f->ctx->stream);
+    });
 }
 
 extern "C" int gfhip_flux_label(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t label_key, size_t count) {
     if (!f) return 1;
     gfhip_context *ctx = f->ctx;
-    const uint64_t keys[4] = {x_key, y_key, z_key, label_key};
     double *columns[4];
-    if (flux_columns(ctx, keys, count, columns)) return 1;
+    if (fp64_columns(ctx, "a flux profile", {x_key, y_key, z_key, label_key}, count, columns)) return 1;
     if (enter(ctx)) return 1;
     gfhip::launch_flux_label(columns[0], columns[1], columns[2], count, f->map, f->packed.get(), columns[3], ctx->stream);
     GFHIP_TRY(ctx, hipGetLastError(), "flux label launch");
@@ -1866,64 +1855,26 @@ extern "C" int gfhip_flux_label(gfhip_flux *f, uint64_t x_key, uint64_t y_key, u
 }
 
 extern "C" int gfhip_flux_counts(gfhip_flux *f, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    if (!f) return 1;
-    gfhip_context *ctx = f->ctx;
-    if (enter(ctx)) return 1;
-    unsigned long long host[3] = {0, 0, 0};
-    GFHIP_TRY(ctx, hipMemcpyAsync(host, f->counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    if (samples) *samples = host[0];
-    if (outside) *outside = host[1];
-    if (skipped) *skipped = host[2];
-    return 0;
+    return f ? f->counts(samples, outside, skipped) : 1;
 }
 
 extern "C" int gfhip_flux_state(gfhip_flux *f, int64_t *limbs) {
     if (!f) return 1;
-    gfhip_context *ctx = f->ctx;
-    if (!limbs) return ctx->fail("gfhip_flux_state needs a destination");
-    if (enter(ctx) || flux_normalise(f)) return 1;
-    GFHIP_TRY(ctx, hipMemcpyAsync(limbs, f->state.get(), f->cells*gfhip::superacc::limbs*sizeof(int64_t), hipMemcpyDeviceToHost,
-                                  ctx->stream), "hipMemcpyAsync(flux profile)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return 0;
+    if (!limbs) return f->ctx->fail("gfhip_flux_state needs a destination");
+    return f->state_to(limbs);
 }
 
 extern "C" int gfhip_flux_merge(gfhip_flux *f, const int64_t *limbs, size_t cells, uint64_t samples, uint64_t outside, uint64_t skipped) {
     if (!f) return 1;
-    gfhip_context *ctx = f->ctx;
-    if (!limbs) return ctx->fail("gfhip_flux_merge needs a state");
-    if (cells != f->cells) return ctx->fail("merge: a flux profile of another shape");
-    if (enter(ctx)) return 1;
-    const size_t words = f->cells*gfhip::superacc::limbs;
-    const unsigned long long counts[3] = {samples, outside, skipped};
-    device_ptr<> other;                                // the incoming limbs, then the three counts
-    GFHIP_TRY(ctx, allocate(other, (words + 3)*sizeof(int64_t)), "hipMalloc(merge)");
-    char *counts_at = static_cast<char *> (other.get()) + words*sizeof(int64_t);
-    GFHIP_TRY(ctx, hipMemcpyAsync(other.get(), limbs, words*sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
-    GFHIP_TRY(ctx, hipMemcpyAsync(counts_at, counts, sizeof(counts), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
-//  Canonical digits (below 2^32) on top of a state that 2^30 deposits may have reached: still inside a limb.
-    gfhip::launch_bins_merge(f->state.get(), other.get(), words, ctx->stream);
-    gfhip::launch_bins_merge(f->counters.get(), counts_at, 3, ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "merge launch");
-    if (flux_normalise(f)) return 1;
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // `other` is freed on return
-    return 0;
+    if (!limbs) return f->ctx->fail("gfhip_flux_merge needs a state");
+    if (cells != f->cells) return f->ctx->fail("merge: a flux profile of another shape");
+    return f->merge(limbs, samples, outside, skipped);
 }
 
 extern "C" int gfhip_flux_read(gfhip_flux *f, double divisor, double *values) {
     if (!f) return 1;
-    gfhip_context *ctx = f->ctx;
-    if (!values) return ctx->fail("gfhip_flux_read needs a destination");
-    if (enter(ctx)) return 1;
-    if (!f->rounded) GFHIP_TRY(ctx, allocate(f->rounded, f->cells*sizeof(double)), "hipMalloc(rounded profile)");
-    if (flux_normalise(f)) return 1;
-    gfhip::launch_bins_round(f->state.get(), f->cells, divisor, f->rounded.get(), ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "round launch");
-    GFHIP_TRY(ctx, hipMemcpyAsync(values, f->rounded.get(), f->cells*sizeof(double), hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpyAsync(rounded profile)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return 0;
+    if (!values) return f->ctx->fail("gfhip_flux_read needs a destination");
+    return f->read(divisor, values);
 }
 
 //  Not through enter(): it reads what gfhip_flux_create decided on the host and touches neither the device nor the stream.

@@ -13,9 +13,9 @@ import os
 import numpy as np
 
 from .backend import GfHipError, key_of
-from .output import ResultFile, write_flux_bins
+from .exact_cells import LIMBS, ExactCells, bin_files
+from .output import write_flux_bins
 
-LIMBS = 67
 SQRT_LABEL = 1
 NO_PRIVATE_SUMS = 2
 TABLE_NAMES = tuple("psi_c%d%d" % (a, b) for a in range(4) for b in range(4))
@@ -73,12 +73,11 @@ def label_host(tables, x, y, z, psi0=None, span=None, sqrt_label=False):
     return label
 
 
-class FluxProfile:
-    """A radial profile of exact sums on a context's device (gfhip_flux_*, include/gf_hip.h)."""
+class FluxProfile(ExactCells):
+    """A radial profile of exact sums on a context's device (gfhip_flux_*, include/gf_hip.h); state() is (cells, 67)."""
+    prefix = "flux"
 
     def __init__(self, context, tables, edges, psi0=None, span=None, sqrt_label=False, private=True):
-        self.context = context
-        self.lib = context.lib
         self.tables = tables
         self.edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
         if self.edges.size < 2:
@@ -88,10 +87,8 @@ class FluxProfile:
         self.private = bool(private)
         given, keep = flux_map(tables, psi0, span, sqrt_label, private)
         self.psi0, self.span = given.psi0, given.span
-        self.handle = self.lib.gfhip_flux_create(context.handle, ctypes.byref(given), self.edges.ctypes.data, self.cells)
+        self._created(context, (self.cells,), ctypes.byref(given), self.edges.ctypes.data, self.cells)
         del keep                                             # the library has copied the tables
-        if not self.handle:
-            raise GfHipError(self.lib.gfhip_last_error(context.handle).decode())
 
     def like(self, context):
         """An empty profile with this one's map, edges and options on another context."""
@@ -101,28 +98,10 @@ class FluxProfile:
     def label_kind(self):
         return "sqrt_s" if self.sqrt_label else "s"
 
-    def add(self, x_key, y_key, z_key, value_key, count):
-        """Bin `count` samples of four fp64 context buffers; asynchronous on the context's stream."""
-        self.context._check(self.lib.gfhip_flux_add(self.handle, key_of(x_key), key_of(y_key), key_of(z_key),
-                                                    key_of(value_key), int(count)))
-
     def label(self, x_key, y_key, z_key, label_key, count):
         """The labels of `count` points into the fp64 buffer `label_key` (NaN outside the map); asynchronous."""
         self.context._check(self.lib.gfhip_flux_label(self.handle, key_of(x_key), key_of(y_key), key_of(z_key),
                                                       key_of(label_key), int(count)))
-
-    def counts(self):
-        """{samples, outside, skipped}: the samples seen, those off the map or the edges (or with a NaN label) and those
-        inside whose value was NaN or infinite."""
-        values = [ctypes.c_uint64() for _ in range(3)]
-        self.context._check(self.lib.gfhip_flux_counts(self.handle, *[ctypes.byref(v) for v in values]))
-        return dict(zip(("samples", "outside", "skipped"), (v.value for v in values)))
-
-    def state(self):
-        """The canonical limbs, shape (cells, 67): identical bytes for the same samples whatever their route."""
-        limbs = np.empty((self.cells, LIMBS), dtype=np.int64)
-        self.context._check(self.lib.gfhip_flux_state(self.handle, limbs.ctypes.data))
-        return limbs
 
     def merge(self, limbs, samples=0, outside=0, skipped=0):
         """Add another profile's state() and counts() (same map and edges: the caller's business)."""
@@ -132,12 +111,6 @@ class FluxProfile:
         self.context._check(self.lib.gfhip_flux_merge(self.handle, limbs.ctypes.data, limbs.shape[0], int(samples), int(outside),
                                                       int(skipped)))
 
-    def read(self, divisor=1.0):
-        """(cells,): the correctly rounded exact sum of each cell, divided by `divisor`."""
-        bins = np.empty(self.cells, dtype=np.float64)
-        self.context._check(self.lib.gfhip_flux_read(self.handle, float(divisor), bins.ctypes.data))
-        return bins
-
     def info(self):
         """How deposits are launched: {private_sums, workgroup_size, cap_cells, max_workgroups, lds_bytes}."""
         info = _Info()
@@ -146,11 +119,6 @@ class FluxProfile:
         out["private_sums"] = bool(out["private_sums"])
         return out
 
-    def close(self):
-        if self.handle and self.context.handle:              # a closed context has freed its profiles
-            self.lib.gfhip_flux_destroy(self.handle)
-        self.handle = None
-
 
 def flux_deposition(directory, num_files, tables, cells, low, high, psi0=None, span=None, sqrt_label=False, private=True,
                     index=0, profile=None):
@@ -158,26 +126,10 @@ def flux_deposition(directory, num_files, tables, cells, low, high, psi0=None, s
     `cells` uniform cells of the label between `low` and `high`, divided by the total number of rays, written to
     <directory>/flux_bins.nc.  Returns (bins, counts).  profile: a FluxProfile that receives the exact state as well."""
     from .backend import Context
-    from . import _lib
     edges = np.linspace(low, high, cells + 1)
     context = Context(index)
     local = FluxProfile(context, tables, edges, psi0, span, sqrt_label, private)
-    names = ("x", "y", "z", "d_power")
-    total = 0
-    for number in range(num_files):
-        file = ResultFile(os.path.join(directory, "result%d.nc" % number))
-        n = file.num_rays
-        total += n
-        keys = ["flux_%s_%d" % (name, n) for name in names]             # one set of buffers per ensemble size
-        for key in keys:
-            context._check(context.lib.gfhip_allocate_buffer(context.handle, key_of(key), n, _lib.GFIR_F64))
-        for record in range(file.records):
-            for name, key in zip(names, keys):
-                context.copy_to_device(key, file.read(name, record))
-            local.add(*keys, n)
-        file.close()
-    bins = local.read(total)
-    counts = local.counts()
+    bins, counts, _ = bin_files(local, directory, num_files, "flux")
     if profile is not None:
         profile.merge(local.state(), **counts)
     psi0, span, kind = local.psi0, local.span, local.label_kind

@@ -379,6 +379,12 @@ class BinsFile(ResultFile):
             self.file = None
 
 
+def _count_attributes(file, samples, outside, skipped):
+    """What became of the samples of a deposition grid or a flux profile, as global integer attributes."""
+    for name, value in (("samples", samples), ("outside", outside), ("skipped", skipped)):
+        file.int64_attribute(name, value)
+
+
 def write_bins(path, bins, xbins, ybins, zbins, samples=0, outside=0, skipped=0):
     """bins.nc of utilities/bin.py: dimensions nx, ny, nz, nxp, nyp, nzp; f8 variables bins(nx, ny, nz), xbins(nxp),
     ybins(nyp), zbins(nzp); and what became of the samples as global integer attributes."""
@@ -391,8 +397,7 @@ def write_bins(path, bins, xbins, ybins, zbins, samples=0, outside=0, skipped=0)
     file.write_variable("bins", bins, ("nx", "ny", "nz"))
     for name, edges, dimension in (("xbins", xbins, "nxp"), ("ybins", ybins, "nyp"), ("zbins", zbins, "nzp")):
         file.write_variable(name, edges, (dimension,))
-    for name, value in (("samples", samples), ("outside", outside), ("skipped", skipped)):
-        file.int64_attribute(name, value)
+    _count_attributes(file, samples, outside, skipped)
     file.close()
 
 
@@ -406,8 +411,7 @@ def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside
     file.create_dimension("nsp", bins.size + 1)
     file.write_variable("bins", bins, ("ns",))
     file.write_variable("sbins", np.asarray(sbins).reshape(-1), ("nsp",))
-    for name, value in (("samples", samples), ("outside", outside), ("skipped", skipped)):
-        file.int64_attribute(name, value)
+    _count_attributes(file, samples, outside, skipped)
     file.float64_attribute("psi0", psi0)
     file.float64_attribute("span", span)
     file.text_attribute("label", label)

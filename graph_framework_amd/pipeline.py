@@ -52,12 +52,9 @@ class OnePass:
         self.iterations = []
         self.records = 0
         self.deposition = deposition
-        self.local = None
-        if deposition is not None:
-            from .deposition import Deposition
-            self.local = Deposition(self.power.context, *deposition.edges)
         self.flux = flux
-        self.local_flux = flux.like(self.power.context) if flux is not None else None
+#  (the caller's, its local twin on the power stage's context), as in absorption.bin_power
+        self.grids = [(target, target.like(self.power.context)) for target in (deposition, flux) if target is not None]
 #  The record as the file takes it, on a stream of its own: the copies to the host overlap what `source` does next.
         self.gather = Context(index)
         self.file = ResultFile(path, n)
@@ -89,10 +86,8 @@ class OnePass:
             power.hand_over(self.source, [(name, keys[name]) for name in _POSITION])
             power.hand_over(absorption, [("kamp", "kamp", 1)])              # reference_imag_variable
             self.power.run()
-        if self.local is not None:
-            self.local.add("x", "y", "z", "d_power", self.num_rays)
-        if self.local_flux is not None:
-            self.local_flux.add("x", "y", "z", "d_power", self.num_rays)
+        for _, local in self.grids:
+            local.add("x", "y", "z", "d_power", self.num_rays)
         gather = self.gather
         gather.hand_over(self.source, [(self._gathered(name), keys[name]) for name, _ in RAY_VARIABLES])
         gather.hand_over(absorption, [(self._gathered("kamp"), "kamp")])
@@ -111,13 +106,9 @@ class OnePass:
             self.sync.join()
         finally:
             self.file.close()
-            if self.local is not None:
-                self.deposition.merge(self.local.state(), **self.local.counts())
-                self.local.close()
-                self.local = None
-            if self.local_flux is not None:
-                self.flux.merge(self.local_flux.state(), **self.local_flux.counts())
-                self.local_flux.close()
-                self.local_flux = None
+            while self.grids:
+                target, local = self.grids.pop(0)
+                target.merge(local.state(), **local.counts())
+                local.close()
             for context in (self.absorption.context, self.power.context, self.gather):
                 context.close()

@@ -229,11 +229,48 @@ def test_misuse_is_refused_before_anything_runs(context):
         deposition.add(*good, 65)
     with pytest.raises(GfHipError, match="unknown buffer"):
         deposition.add(good[0], good[1], "no such buffer", good[3], 64)
+    lib = context.lib
+    for call, arguments in ((lib.gfhip_bins_state, (None,)), (lib.gfhip_bins_merge, (None, 1, 0, 0)),
+                            (lib.gfhip_bins_read, (1.0, None))):
+        assert call(deposition.handle, *arguments) == 1                                 # a null pointer on a live grid
+    for call, arguments in ((lib.gfhip_bins_add, (1, 2, 3, 4, 1)), (lib.gfhip_bins_counts, (None, None, None)),
+                            (lib.gfhip_bins_state, (None,)), (lib.gfhip_bins_merge, (None, 0, 0, 0)),
+                            (lib.gfhip_bins_read, (1.0, None))):
+        assert call(None, *arguments) == 1                                              # a null grid
+    lib.gfhip_bins_destroy(None)
     assert deposition.counts() == dict(samples=0, outside=0, skipped=0)                 # nothing was launched
     assert not deposition.state().any()
     deposition.add(*good, 64)                                                           # and the grid still works
     check(deposition, Oracle(EDGES).add(*columns))
     deposition.close()
+
+
+def test_like_gives_an_empty_twin_whose_state_merges_back(context):
+    """64*3 + 5 samples: half added to the grid, half to its twin on another context and merged, against all of them
+    added to one grid directly."""
+    from graph_framework_amd import Context
+    from graph_framework_amd.deposition import Deposition
+    n = 64*3 + 5
+    columns = edge_samples(n, 51)
+    direct = Deposition(context, *EDGES)
+    direct.add(*upload(context, "like_all", columns), n)
+    original = Deposition(context, *EDGES)
+    original.add(*upload(context, "like_first", [c[:100] for c in columns]), 100)
+    elsewhere = Context(0)
+    twin = original.like(elsewhere)
+    assert twin.context is elsewhere and twin.handle != original.handle
+    assert twin.shape == original.shape == (3, 2, 2)
+    assert all(np.array_equal(ours, theirs) for ours, theirs in zip(twin.edges, original.edges)) and len(twin.edges) == 3
+    assert twin.counts() == dict(samples=0, outside=0, skipped=0) and not twin.state().any()
+    twin.add(*upload(elsewhere, "like_rest", [c[100:] for c in columns]), n - 100)
+    original.merge(twin.state(), **twin.counts())
+    assert original.state().tobytes() == direct.state().tobytes()
+    assert original.counts() == direct.counts()
+    check(original, Oracle(EDGES).add(*columns))
+    twin.close()
+    elsewhere.close()
+    original.close()
+    direct.close()
 
 
 def _read_bins(path):

@@ -226,6 +226,71 @@ def test_same_bytes_whatever_the_route(context, tables, pool):
         each.close()
 
 
+def edges_on_labels(pool, cells):
+    """cells + 1 edges whose first, last and (with more than one cell) one inner edge are labels of the pool's points:
+    (edges, the pool indices of those points, their labels)."""
+    _, labels = pool
+    finite = np.unique(labels[(labels > 0.2) & (labels < 0.8)])
+    first, inner, last = finite[1], finite[finite.size//2], finite[-2]
+    edges = np.linspace(first, last, cells + 1)
+    on = [first, last]
+    if cells > 1:
+        at = int(np.searchsorted(edges, inner))                             # edges[at - 1] < inner <= edges[at]
+        assert 0 < at < cells
+        edges[at] = inner
+        on = [first, inner, last]
+    assert edges[0] == first and edges[-1] == last and (np.diff(edges) > 0.0).all()
+    return edges, [int(np.flatnonzero(labels == label)[0]) for label in on], np.array(on)
+
+
+@pytest.mark.parametrize("private", [True, False], ids=["private", "global"])
+@pytest.mark.parametrize("cells", [1, 256, 257])
+def test_the_grid_and_the_profile_are_one_rule(context, tables, pool, cells, private):
+    """The profile's own labels binned as the x column of a 3-D grid with the profile's edges (y and z: one cell around
+    zeros) give the profile's bytes: deposit_kernel, flux_deposit_kernel<true> (1 and 256 cells) and
+    flux_deposit_kernel<false> are three callers of the pieces of csrc/cell_deposit.hpp.  2*1024 + 37 samples: more
+    than one private workgroup, a multiple of neither 64 nor 1024."""
+    from graph_framework_amd.deposition import Deposition
+    from graph_framework_amd.flux import FluxProfile
+    (px, py, pz), labels = pool
+    n = 2*1024 + 37
+    edges, on, on_labels = edges_on_labels(pool, cells)
+    columns = samples(pool, n, 300 + cells)                                # mixed and wave-uniform blocks, off-map points
+    inside = on[0]                                                          # on the first edge: in cell 0
+    specials = [0.0, -0.0, 15e-324, 1.797e308, -1.797e308, 1.797e308, np.nan, np.inf, -np.inf, 2.0**-1060]
+    for c, p in zip(columns[:3], (px, py, pz)):
+        c[200:200 + len(specials)] = p[inside]
+        c[220:220 + len(on)] = p[on]                                        # exactly on an edge; the last one on the last edge
+        c[128:192] = p[inside]                                              # one whole wave of identical samples
+    columns[3][200:200 + len(specials)] = specials
+    columns[3][220:220 + len(on)] = 1.5
+    columns[3][128:192] = 0.1
+    picked = flux_model.label(tables, *columns[:3])
+    assert np.isnan(picked).any()                                           # points off the map
+    assert (picked[220:220 + len(on)] == on_labels).all() and np.isin(on_labels, edges).all() and on_labels[-1] == edges[-1]
+
+    profile = FluxProfile(context, tables, edges, private=private)
+    assert profile.info()["private_sums"] == (private and cells <= 256)
+    keys = upload(context, "rule%d" % cells, columns)
+    label_key = upload(context, "rule_label%d" % cells, [np.zeros(n)], ("label",))[0]
+    profile.label(*keys[:3], label_key, n)
+    device_labels = np.empty(n)
+    context.copy_to_host(label_key, device_labels)
+    same_bits(device_labels, picked)
+    profile.add(*keys, n)
+
+    grid = Deposition(context, edges, np.array([-1.0, 1.0]), np.array([-1.0, 1.0]))
+    grid_keys = upload(context, "rule_grid%d" % cells, [device_labels, np.zeros(n), np.zeros(n), columns[3]])
+    grid.add(*grid_keys, n)
+    counts = profile.counts()
+    assert counts["samples"] == n and counts["outside"] >= int(np.isnan(picked).sum()) + 1 and counts["skipped"] >= 3
+    assert grid.state().reshape(cells, 67).tobytes() == profile.state().tobytes() and profile.state().any()
+    assert grid.counts() == counts
+    same_bits(grid.read(3.0).reshape(cells), profile.read(3.0))
+    grid.close()
+    profile.close()
+
+
 def test_records_accumulate_and_state_does_not_disturb_them(context, tables, pool):
     from graph_framework_amd.flux import FluxProfile
     edges = edges_for("cap", pool)
