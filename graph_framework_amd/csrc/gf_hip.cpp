@@ -42,8 +42,7 @@
 namespace gfhip {
 void launch_max_reduce(const void *in, const size_t n, const bool f64,
                        unsigned long long *result, const unsigned int num_cus, hipStream_t stream);
-void launch_converge_decide(const bool f64, unsigned long long *reduced, void *state, hipStream_t stream);
-void launch_converge_decide_batch(const bool f64, unsigned long long *reduced, void *state, const unsigned int count, hipStream_t stream);
+void launch_converge_decide(const bool f64, unsigned long long *reduced, void *state, const unsigned int count, hipStream_t stream);
 void launch_max_modulus(const void *in, const size_t n, const bool f64, void *result, hipStream_t stream);
 }
 
@@ -859,18 +858,8 @@ extern "C" int gfhip_run(gfhip_kernel *k, uint32_t steps) {
     return launch(k, gfhip::entry::plain, steps);
 }
 
-static double decode_ordered(const unsigned long long key, const bool f64) {
-    if (f64) {
-        const unsigned long long bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-        double v;
-        std::memcpy(&v, &bits, 8);
-        return v;
-    }
-    const unsigned int k32 = static_cast<unsigned int> (key);
-    const unsigned int bits = (k32 >> 31) ? (k32 & 0x7FFFFFFFu) : ~k32;
-    float v;
-    std::memcpy(&v, &bits, 4);
-    return static_cast<double> (v);
+static double decode_max(const unsigned long long key, const bool f64) {
+    return f64 ? gfhip::from_ordered_key<double> (key) : static_cast<double> (gfhip::from_ordered_key<float> (key));
 }
 
 //  One pass + the max of its last output left in ctx->device_scalar (ordered image), no sync:
@@ -893,7 +882,7 @@ static int read_max(gfhip_context *ctx, const bool f64, double *value) {
     GFHIP_TRY(ctx, hipMemcpyAsync(ctx->host_scalar.get(), ctx->device_scalar.get(), sizeof(unsigned long long),
                                   hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    *value = decode_ordered(*ctx->host_scalar, f64);
+    *value = decode_max(*ctx->host_scalar, f64);
     return 0;
 }
 
@@ -978,68 +967,38 @@ extern "C" int gfhip_run_max(gfhip_kernel *k, double *max_value) {
     return 0;
 }
 
-//  workflow::converge_item::run, workflow.hpp:179-205, in the item's own type, one host
-//  synchronisation per pass: the form for items without `<name>_max` and for empty ensembles.
+//  One pass and its max in the item's own type V: through the C ABI's entries, so that a streak of them runs ahead.
+//  The second value is what gfhip_converge reports of it: the value itself, the modulus of a complex one.
 template<typename T>
-static int converge_loop(gfhip_kernel *k, const double tolerance_, const size_t max_iterations,
-                         size_t *iterations_out, double *last_max) {
-    const T tolerance = static_cast<T> (tolerance_);
-    size_t iterations = 0;
-    double value;
-    if (gfhip_run_max(k, &value)) return 1;
-    T max_residual = static_cast<T> (value);
-    T last = std::numeric_limits<T>::max();
-    T off_last = std::numeric_limits<T>::max();
-    while (std::abs(max_residual) > std::abs(tolerance)            &&
-           std::abs(last - max_residual) > std::abs(tolerance)     &&
-           std::abs(off_last - max_residual) > std::abs(tolerance) &&
-           iterations++ < max_iterations) {
-        last = max_residual;
-        if (!(iterations%2)) {
-            off_last = max_residual;
-        }
-        if (gfhip_run_max(k, &value)) return 1;
-        max_residual = static_cast<T> (value);
-    }
-    if (iterations_out) *iterations_out = iterations;
-    if (last_max) *last_max = static_cast<double> (max_residual);
+static int pass_with_max(gfhip_kernel *k, T &max, double &reported) {
+    if (gfhip_run_max(k, &reported)) return 1;
+    max = static_cast<T> (reported);
+    reported = static_cast<double> (max);
+    return 0;
+}
+template<typename B>
+static int pass_with_max(gfhip_kernel *k, std::complex<B> &max, double &reported) {
+    double value[2];
+    if (gfhip_run_max_complex(k, value)) return 1;
+    max = std::complex<B> (static_cast<B> (value[0]), static_cast<B> (value[1]));
+    reported = static_cast<double> (gfhip::mag(max));
     return 0;
 }
 
-//  std::abs of a complex value as the reference's build has it: the C library's cabs, that is hypot.  In a HIP
-//  translation unit std::abs(std::complex) is the textbook scaled formula instead (the compiler's complex wrapper
-//  turns the C99 functions off): NaN for an infinite part, and not always hypot's last bit.
-template<typename B>
-static B modulus(const std::complex<B> &z) {
-    return std::hypot(z.real(), z.imag());
-}
-
-//  ... for complex items (max = the element of largest modulus; the loop compares moduli,
-//  workflow.hpp:183-186 with T = std::complex).
-template<typename B>
-static int converge_loop_complex(gfhip_kernel *k, const double tolerance_, const size_t max_iterations,
-                                 size_t *iterations_out, double *last_max) {
-    typedef std::complex<B> T;
-    const T tolerance(static_cast<B> (tolerance_), 0);
-    size_t iterations = 0;
-    double value[2];
-    if (gfhip_run_max_complex(k, value)) return 1;
-    T max_residual(static_cast<B> (value[0]), static_cast<B> (value[1]));
-    T last = std::numeric_limits<T>::max();            // std::numeric_limits<std::complex> is the unspecialised one: T()
-    T off_last = std::numeric_limits<T>::max();
-    while (modulus(max_residual) > modulus(tolerance)            &&
-           modulus(last - max_residual) > modulus(tolerance)     &&
-           modulus(off_last - max_residual) > modulus(tolerance) &&
-           iterations++ < max_iterations) {
-        last = max_residual;
-        if (!(iterations%2)) {
-            off_last = max_residual;
-        }
-        if (gfhip_run_max_complex(k, value)) return 1;
-        max_residual = T(static_cast<B> (value[0]), static_cast<B> (value[1]));
-    }
-    if (iterations_out) *iterations_out = iterations;
-    if (last_max) *last_max = static_cast<double> (modulus(max_residual));
+//  workflow::converge_item::run, workflow.hpp:179-205, in the item's own type (converge_state.hpp has the loop's
+//  test), one host synchronisation per pass: the form for complex items (max = the element of largest modulus; the
+//  loop compares moduli), for items without `<name>_max` and for empty ensembles.
+template<typename V>
+static int converge_loop(gfhip_kernel *k, const double tolerance, const size_t max_iterations,
+                         size_t *iterations_out, double *last_max) {
+    gfhip::converge_step<V> step(tolerance, max_iterations);
+    V max_residual;
+    double reported;
+    do {
+        if (pass_with_max(k, max_residual, reported)) return 1;
+    } while (step.advance(max_residual));
+    if (iterations_out) *iterations_out = static_cast<size_t> (step.iterations);
+    if (last_max) *last_max = reported;
     return 0;
 }
 
@@ -1062,15 +1021,15 @@ static int ensure_undo(gfhip_kernel *k) {
     return 0;
 }
 
-//  Back to the state of the beginning of the last batch.
-static int restore_undo(gfhip_kernel *k) {
+//  Back to the state of the beginning of the last batch, then only its first `keep` passes: the ones that count.
+static int take_back(gfhip_kernel *k, const unsigned int keep) {
     gfhip_context *ctx = k->ctx;
     for (size_t s = 0; s < k->item.setters.size(); s++) {
         void *target = ctx->buffers[k->input_keys[k->item.setters[s].input]].pointer;
         GFHIP_TRY(ctx, hipMemcpyAsync(target, k->undo[s].get(), k->num_rays*k->item.element_size(), hipMemcpyDeviceToDevice,
                                       ctx->stream), "hipMemcpyAsync(undo)");
     }
-    return 0;
+    return launch_batch(k, keep, nullptr);
 }
 
 //  gfhip_run_max called again and again with nothing in between is the reference's converge loop seen from below
@@ -1088,9 +1047,7 @@ static int settle(gfhip_context *ctx) {
     const unsigned int asked = k->ahead_taken, ran = static_cast<unsigned int> (k->ahead.size());
     k->ahead.clear();
     k->ahead_taken = 0;
-    if (asked == ran) return 0;
-    if (restore_undo(k)) return 1;
-    return launch_batch(k, asked, nullptr);
+    return asked == ran ? 0 : take_back(k, asked);
 }
 
 static int run_max_ahead(gfhip_kernel *k, double *max_value, bool &answered) {
@@ -1113,7 +1070,7 @@ static int run_max_ahead(gfhip_kernel *k, double *max_value, bool &answered) {
                                   hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     k->ahead.clear();
-    for (unsigned int b = 0; b < batch; b++) k->ahead.push_back(decode_ordered(ctx->host_scalar.get()[b], k->item.dtype == GFIR_F64));
+    for (unsigned int b = 0; b < batch; b++) k->ahead.push_back(decode_max(ctx->host_scalar.get()[b], k->item.dtype == GFIR_F64));
     k->ahead_taken = 1;
     ctx->running_ahead = k;
     *max_value = k->ahead[0];
@@ -1121,7 +1078,15 @@ static int run_max_ahead(gfhip_kernel *k, double *max_value, bool &answered) {
     return 0;
 }
 
-//  The same loop with its test on the device (reduce.hip: converge_decide_kernel): passes are
+//  One launch of `passes` passes, the max of each left in ctx->device_scalar[pass] (ordered image), no sync.
+static int enqueue_passes_with_max(gfhip_kernel *k, const unsigned int passes, const unsigned int *stop) {
+    return passes > 1 ? launch_batch(k, passes, stop) : enqueue_pass_with_max(k, stop);
+}
+
+//  Launches per host synchronisation in converge_on_device, the first time and at most: of one pass, of several.
+static const size_t queue_depth[2][2] = {{16, 64}, {6, 24}};
+
+//  The same loop with its test on the device (converge_state.hpp: decide): passes are
 //  enqueued ahead of the host in growing batches, each followed by the one-thread test; once
 //  the test has come out false the passes still queued return at once (`stop`), so exactly the
 //  passes of the host loop run, with the same iteration count — and the host synchronises once
@@ -1130,7 +1095,7 @@ static int run_max_ahead(gfhip_kernel *k, double *max_value, bool &answered) {
 //  Items with `<name>_batch` (codegen.hpp) run several passes per launch.  A pass of this loop
 //  only feeds the next pass of the same ray and the max the loop's test looks at, so a launch may run a
 //  few passes on state kept in registers — each pass leaving its own max — and the test (on the device,
-//  reduce.hip: converge_decide_batch_kernel) is applied to those maxima in order afterwards.  If the loop
+//  the same decide) is applied to those maxima in order afterwards.  If the loop
 //  turns out to have ended before the last pass of a batch, the state of the beginning of that batch is
 //  restored from the undo arrays and the batch is redone with exactly the passes the loop ran: the same
 //  passes, iteration count, state and output as one launch per pass, at a third of the sweeps over the
@@ -1141,31 +1106,21 @@ static int converge_on_device(gfhip_kernel *k, const double tolerance, const siz
     const bool f64 = k->item.dtype == GFIR_F64;
     const unsigned int batch = k->whole.batch_function ? k->whole.low.batch : 1;        // passes per launch
     if (batch > 1 && ensure_undo(k)) return 1;
-    const size_t reduce_words = batch > 1 ? 8 : 1;
     gfhip::converge_state &host = *ctx->host_converge;
-    host = gfhip::converge_state();
-    host.last = host.off_last = f64 ? std::numeric_limits<double>::max()
-                                    : static_cast<double> (std::numeric_limits<float>::max());
-    host.tolerance = tolerance;
-    host.limit = max_iterations;
+    host = f64 ? gfhip::converge_begin<double> (tolerance, max_iterations) : gfhip::converge_begin<float> (tolerance, max_iterations);
     GFHIP_TRY(ctx, hipMemcpyAsync(ctx->device_converge.get(), &host, sizeof(host), hipMemcpyHostToDevice, ctx->stream),
               "hipMemcpyAsync(converge state)");
-    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, reduce_words*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
+    GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, 8*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
     GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");     // `host` is written again below
     const unsigned int *stop = &ctx->device_converge->done;
     const uint64_t first_launch = k->launch_count;
     const size_t events_before = k->events.size();
-    size_t queued = batch > 1 ? 6 : 16;                    // launches per host synchronisation, growing
-    const size_t most = batch > 1 ? 24 : 64;
+    size_t queued = queue_depth[batch > 1][0];             // growing
+    const size_t most = queue_depth[batch > 1][1];
     for (;;) {
         for (size_t q = 0; q < queued; q++) {
-            if (batch > 1) {
-                if (launch_batch(k, batch, stop)) return 1;
-                gfhip::launch_converge_decide_batch(f64, ctx->device_scalar.get(), ctx->device_converge.get(), batch, ctx->stream);
-            } else {
-                if (enqueue_pass_with_max(k, stop)) return 1;
-                gfhip::launch_converge_decide(f64, ctx->device_scalar.get(), ctx->device_converge.get(), ctx->stream);
-            }
+            if (enqueue_passes_with_max(k, batch, stop)) return 1;
+            gfhip::launch_converge_decide(f64, ctx->device_scalar.get(), ctx->device_converge.get(), batch, ctx->stream);
             GFHIP_TRY(ctx, hipGetLastError(), "converge_decide launch");
         }
         GFHIP_TRY(ctx, hipMemcpyAsync(&host, ctx->device_converge.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream),
@@ -1189,7 +1144,7 @@ static int converge_on_device(gfhip_kernel *k, const double tolerance, const siz
     }
     if (host.extra) {
 //  The loop ended inside the last batch: back to the state of its beginning, then only the loop's passes.
-        if (restore_undo(k) || launch_batch(k, host.batch_passes, nullptr)) return 1;
+        if (take_back(k, host.batch_passes)) return 1;
         GFHIP_TRY(ctx, hipMemsetAsync(ctx->device_scalar.get(), 0, 8*sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
         GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     }
@@ -1208,8 +1163,8 @@ extern "C" int gfhip_converge(gfhip_kernel *k, double tolerance, size_t max_iter
     double residual = 0.0;
     int status;
     if (k->item.is_complex()) {
-        status = k->item.base_is_f64() ? converge_loop_complex<double> (k, tolerance, max_iterations, &used, &residual)
-                                       : converge_loop_complex<float> (k, tolerance, max_iterations, &used, &residual);
+        status = k->item.base_is_f64() ? converge_loop<std::complex<double>> (k, tolerance, max_iterations, &used, &residual)
+                                       : converge_loop<std::complex<float>> (k, tolerance, max_iterations, &used, &residual);
     } else if (k->whole.max_function && k->num_rays > 0) {             // (every item with `<name>_batch` has `<name>_max`)
         status = converge_on_device(k, tolerance, max_iterations, &used, &residual);
     } else if (k->item.dtype == GFIR_F64) {

@@ -1,6 +1,8 @@
 //------------------------------------------------------------------------------
 ///  @file reduce.hip
-///  @brief Device-wide max reduction for converge items (hand-written, gfx950).
+///  @brief Device-wide max reduction for converge items (hand-written, gfx950): max_reduce_kernel for real outputs,
+///  max_modulus_kernel for complex ones, and converge_decide_kernel, the launch around the loop's test on the
+///  device (converge_state.hpp, which also has the integer image `ordered_key` the maxima travel in).
 ///
 ///  Replaces the reference's generated `max_reduction` kernel
 ///  (cuda_context.hpp:954-995: one block of 1024 threads, 32-wide shuffles, result
@@ -22,17 +24,6 @@
 #include "converge_state.hpp"
 
 namespace gfhip {
-
-//  Monotone map real -> unsigned so that integer max == floating max.
-__device__ __forceinline__ unsigned long long ordered(const double x) {
-    const unsigned long long b = static_cast<unsigned long long> (__double_as_longlong(x));
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ unsigned long long ordered(const float x) {
-    const unsigned int b = __float_as_uint(x);
-    const unsigned int k = (b >> 31) ? ~b : (b | 0x80000000u);
-    return static_cast<unsigned long long> (k);
-}
 
 template<typename T> struct alignas(2*sizeof(T)) vec2 { T a, b; };
 
@@ -89,108 +80,24 @@ max_reduce_kernel(const T *__restrict__ base, const unsigned long long total, co
         for (unsigned int w = 1; w < (blockDim.x >> 6); w++) {
             block = wave_max[w] > block ? wave_max[w] : block;
         }
-        atomicMax(result, ordered(block));
+        atomicMax(result, ordered_key(block));
         if (blockIdx.x == 0 && first_is_nan) atomicMax(result, ~0ull >> (sizeof(T) == 8 ? 0 : 32));
     }
 }
 
-//  Device side of workflow::converge_item::run (workflow.hpp:179-205): one thread applies the
-//  loop's test to the max the pass has just reduced, in the item's own precision, and either
-//  stops the loop (`done`; later passes of the batch return at once) or advances its state.
-//      while (|max| > tol && |last - max| > tol && |off_last - max| > tol && iterations++ < limit) {
-//          last = max;  if (!(iterations%2)) off_last = max;  max = run_max(); }
-
+//  Device side of the converge loop (converge_state.hpp: decide): one thread applies the loop's test to the maxima
+//  the `count` passes of the launch before it have reduced.
 template<typename T>
-__global__ void converge_decide_kernel(unsigned long long *__restrict__ reduced, converge_state *__restrict__ state) {
-    if (state->done) return;
-    const unsigned long long key = *reduced;
-    *reduced = 0ull;                                   // ready for the next pass's atomicMax
-    T value;
-    if (sizeof(T) == 8) {
-        const unsigned long long bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-        value = static_cast<T> (__longlong_as_double(static_cast<long long> (bits)));
-    } else {
-        const unsigned int k32 = static_cast<unsigned int> (key);
-        const unsigned int bits = (k32 >> 31) ? (k32 & 0x7FFFFFFFu) : ~k32;
-        value = static_cast<T> (__uint_as_float(bits));
-    }
-    const T tolerance = static_cast<T> (state->tolerance);
-    const T last = static_cast<T> (state->last), off_last = static_cast<T> (state->off_last);
-    state->max_residual = static_cast<double> (value);
-    state->passes++;
-    const T zero = static_cast<T> (0);
-    const T a = value < zero ? -value : value, t = tolerance < zero ? -tolerance : tolerance;
-    const T dl = last - value, dol = off_last - value;
-    bool go = a > t && (dl < zero ? -dl : dl) > t && (dol < zero ? -dol : dol) > t;
-    if (go) {
-        go = state->iterations < state->limit;
-        state->iterations++;
-    }
-    if (go) {
-        state->last = static_cast<double> (value);
-        if (!(state->iterations%2ull)) state->off_last = static_cast<double> (value);
-    } else {
-        state->done = 1u;
-    }
+__global__ void converge_decide_kernel(unsigned long long *__restrict__ reduced, converge_state *__restrict__ state,
+                                       const unsigned int count) {
+    decide<T> (*state, reduced, count);
 }
 
-//  The same test applied to the maxima of a batch of passes, in order (`<name>_batch`, codegen.hpp): the loop
-//  may end on any of them.  If it ends before the last pass of the batch, `extra` passes ran that the host loop
-//  would not have run; the host restores the state of the beginning of the batch and redoes `batch_passes`.
-template<typename T>
-__global__ void converge_decide_batch_kernel(unsigned long long *__restrict__ reduced, converge_state *__restrict__ state,
-                                             const unsigned int count) {
-    if (state->done) return;
-    const T tolerance = static_cast<T> (state->tolerance);
-    const T zero = static_cast<T> (0);
-    const T t = tolerance < zero ? -tolerance : tolerance;
-    for (unsigned int pass = 0; pass < count; pass++) {
-        const unsigned long long key = reduced[pass];
-        reduced[pass] = 0ull;
-        if (state->done) continue;                   // still clear the slots of the passes beyond the end
-        T value;
-        if (sizeof(T) == 8) {
-            const unsigned long long bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-            value = static_cast<T> (__longlong_as_double(static_cast<long long> (bits)));
-        } else {
-            const unsigned int k32 = static_cast<unsigned int> (key);
-            const unsigned int bits = (k32 >> 31) ? (k32 & 0x7FFFFFFFu) : ~k32;
-            value = static_cast<T> (__uint_as_float(bits));
-        }
-        const T last = static_cast<T> (state->last), off_last = static_cast<T> (state->off_last);
-        state->max_residual = static_cast<double> (value);
-        state->passes++;
-        const T a = value < zero ? -value : value;
-        const T dl = last - value, dol = off_last - value;
-        bool go = a > t && (dl < zero ? -dl : dl) > t && (dol < zero ? -dol : dol) > t;
-        if (go) {
-            go = state->iterations < state->limit;
-            state->iterations++;
-        }
-        if (go) {
-            state->last = static_cast<double> (value);
-            if (!(state->iterations%2ull)) state->off_last = static_cast<double> (value);
-        } else {
-            state->done = 1u;
-            state->batch_passes = pass + 1u;
-            state->extra = count - (pass + 1u);
-        }
-    }
-}
-
-void launch_converge_decide_batch(const bool f64, unsigned long long *reduced, void *state, const unsigned int count, hipStream_t stream) {
+void launch_converge_decide(const bool f64, unsigned long long *reduced, void *state, const unsigned int count, hipStream_t stream) {
     if (f64) {
-        hipLaunchKernelGGL(converge_decide_batch_kernel<double>, dim3(1), dim3(1), 0, stream, reduced, static_cast<converge_state *> (state), count);
+        hipLaunchKernelGGL(converge_decide_kernel<double>, dim3(1), dim3(1), 0, stream, reduced, static_cast<converge_state *> (state), count);
     } else {
-        hipLaunchKernelGGL(converge_decide_batch_kernel<float>, dim3(1), dim3(1), 0, stream, reduced, static_cast<converge_state *> (state), count);
-    }
-}
-
-void launch_converge_decide(const bool f64, unsigned long long *reduced, void *state, hipStream_t stream) {
-    if (f64) {
-        hipLaunchKernelGGL(converge_decide_kernel<double>, dim3(1), dim3(1), 0, stream, reduced, static_cast<converge_state *> (state));
-    } else {
-        hipLaunchKernelGGL(converge_decide_kernel<float>, dim3(1), dim3(1), 0, stream, reduced, static_cast<converge_state *> (state));
+        hipLaunchKernelGGL(converge_decide_kernel<float>, dim3(1), dim3(1), 0, stream, reduced, static_cast<converge_state *> (state), count);
     }
 }
 

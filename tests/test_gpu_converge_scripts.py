@@ -112,6 +112,53 @@ def test_device_decided_loop(monkeypatch, capfd, dtype, batch):
         context.close()
 
 
+def sampled_launches(count, passes, batch, every):
+    """(event pairs one Kernel.converge leaves, the kernel's launch count afterwards), from the count before it.
+    The loop queues 16, 32, 64, ... single passes (6, 12, 24, ... launches of `batch` passes) per host synchronisation
+    until the test has come out false; every queued launch takes a number, the `every`-th ones are bracketed, and of
+    those only the pairs of the ceil(passes/batch) launches that ran are kept.  A loop that ended inside a launch
+    redoes that launch: one more number, one more pair if it is an `every`-th."""
+    ran = -(-passes//batch)
+    queued, most = (6, 24) if batch > 1 else (16, 64)
+    total = queued
+    while total < ran:
+        queued = min(2*queued, most)
+        total += queued
+    kept = sum(1 for launch in range(count, count + ran) if launch % every == 0)
+    count += total
+    if batch > 1 and passes % batch:
+        kept += count % every == 0
+        count += 1
+    return kept, count
+
+
+@pytest.mark.parametrize("batch", [1, 3])
+def test_device_decided_loop_keeps_the_timing_of_the_launches_that_ran(monkeypatch, batch):
+    """Launch timing under Kernel.converge: one sample per launch that ran — not per launch that was queued and
+    returned at once — plus the redo launch; around every launch, then around every second one."""
+    monkeypatch.setenv("GFHIP_CONVERGE_BATCH", str(batch))
+    dtype, rays = "f64", 300
+    context, kernel = make(dtype, rays)
+    assert int(kernel.info().converge_batch) == (batch if batch > 1 else 0)
+    count = 0
+    for every in (1, 2):
+        context.enable_timing(True, every)
+        for case in expected(dtype, rays):
+            load(context, case.columns)
+            assert kernel.converge(case.tolerance, case.limit)[0] == case.iterations, case.name
+            samples = kernel.timing_samples()
+            want, count = sampled_launches(count, case.passes, batch, every)
+            print(case.name, "every", every, "passes", case.passes, "samples", len(samples), "want", want)
+            assert len(samples) == want, (case.name, every)
+            if every == 1:
+                assert want == -(-case.passes//batch) + (batch > 1 and case.passes % batch != 0), case.name
+            assert all(ms >= 0.0 for ms in samples), case.name
+#  Nothing is left pending: no event pair of a launch that returned at once stayed behind.
+            assert kernel.timing() == (0.0, 0), (case.name, every)
+            assert kernel.timing_samples() == [], (case.name, every)
+    context.close()
+
+
 @pytest.mark.parametrize("between", ["streak", "wait"])
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_host_loop_on_run_max(dtype, between):
@@ -162,7 +209,7 @@ def test_host_decided_loop_of_a_long_item(capfd, dtype):
 
 @pytest.mark.parametrize("dtype", ["c32", "c64"])
 def test_complex_loop(capfd, dtype):
-    """converge_loop_complex: the element of largest modulus, the loop on moduli; last and off_last start at 0."""
+    """converge_loop<std::complex>: the element of largest modulus, the loop on moduli; last and off_last start at 0."""
     kind = NUMPY[dtype]
     for rays in (2, 300):
         context, kernel = make(dtype, rays)
