@@ -8,6 +8,7 @@ with a record every `sub_steps`, result<rank>.nc) on the MI355X backend.
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4 --one-pass
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --one-pass
+    python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --flux-density 16 --flux-window 1.0,2.4,-1.0,1.0
     python examples/trace_rays.py --equilibrium vmec --rays 20000 --steps 10 --sub-steps 2 --output /tmp/vmec_rays
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/trace_rays.py ...
 
@@ -18,7 +19,8 @@ the same file: calculate_power (kamp per stored record) and bin_power (power, d_
 --bin-box as well, bin_power also bins d_power on that grid as it goes (utilities/bin.py's profile, exact sums)
 and the rank writes <output>_bins<rank>.nc: its own rays' sums divided by its own ray count.
 With --flux-bins and --flux-tables (alone or next to --bins) d_power is also binned on flux surfaces
-(graph_framework_amd/flux.py) and the rank writes <output>_flux<rank>.nc.
+(graph_framework_amd/flux.py) and the rank writes <output>_flux<rank>.nc; with --flux-density [SUB] (and --flux-window)
+the file also holds the cells' volumes and the power density, bins/volume.
 With --one-pass as well the same work items run on every record while the trace holds it in device memory
 (graph_framework_amd/pipeline.py): same file, same bits, written once, and no pass over the file afterwards.
 """
@@ -67,6 +69,11 @@ def main():
                         help="the EFIT tables under efit.nc's dataset names (psi_c00 .. psi_c33, rmin, dr, zmin, dz, psimin, dpsi)")
     parser.add_argument("--flux-range", default="0,1", metavar="LOW,HIGH", help="the label range the cells divide")
     parser.add_argument("--flux-sqrt", action="store_true", help="label sqrt((psi - psimin)/span) instead of (psi - psimin)/span")
+    parser.add_argument("--flux-density", type=int, nargs="?", const=16, default=None, metavar="SUB",
+                        help="with --flux-bins: also the cells' volumes (every table cell cut into SUB x SUB, default 16) and "
+                             "the power density bins/volume, as volume and density in <output>_flux<rank>.nc")
+    parser.add_argument("--flux-window", default=None, metavar="RLO,RHI,ZLO,ZHI",
+                        help="with --flux-density: only the part of the map with RLO <= R < RHI and ZLO <= z < ZHI counts as volume")
     parser.add_argument("--one-pass", action="store_true",
                         help="with --output and --absorption-model: kamp, power and the bins of every record while the rays are "
                              "traced, instead of two more passes over the file")
@@ -77,6 +84,10 @@ def main():
         parser.error("--flux-bins and --flux-tables go together")
     if args.flux_bins is not None and not (args.output and args.absorption_model):
         parser.error("--flux-bins needs --output and --absorption-model")
+    if args.flux_density is not None and args.flux_bins is None:
+        parser.error("--flux-density needs --flux-bins")
+    if args.flux_window is not None and args.flux_density is None:
+        parser.error("--flux-window needs --flux-density")
     if args.one_pass and not (args.output and args.absorption_model):
         parser.error("--one-pass needs --output and --absorption-model")
 
@@ -133,9 +144,14 @@ def main():
         counts = profile.counts()
         bins = profile.read(end - begin)
         edges, psi0, span, kind = profile.edges, profile.psi0, profile.span, profile.label_kind
+        extra = {}
+        if args.flux_density is not None:
+            from graph_framework_amd.flux import density_variables
+            window = [float(v) for v in args.flux_window.split(",")] if args.flux_window else None
+            extra = density_variables(profile, bins, args.flux_density, window)
         profile.close()
         context.close()
-        write_flux_bins("%s_flux%d.nc" % (args.output, rank), bins, edges, psi0, span, kind, **counts)
+        write_flux_bins("%s_flux%d.nc" % (args.output, rank), bins, edges, psi0, span, kind, **counts, **extra)
         print("rank %d: flux profile on %d cells of %s: %d samples, %d outside, %d skipped; sum of bins %.6e"
               % (rank, bins.size, kind, counts["samples"], counts["outside"], counts["skipped"], float(bins.sum())))
 

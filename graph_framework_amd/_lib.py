@@ -98,6 +98,8 @@ SYMBOLS = [
     ("gfhip_flux_info", _I, [_P, _P]),
     ("gfhip_flux_destroy", None, [_P]),
     ("gfhip_flux_label_host", _I, [_P, _P, _P, _P, _S, _P]),
+    ("gfhip_flux_add_volumes", _I, [_P, _U32, _P, _U64, _U64]),
+    ("gfhip_flux_volumes_host", _I, [_P, _P, _S, _U32, _P, _U64, _U64, _P, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 

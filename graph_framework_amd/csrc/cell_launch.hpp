@@ -30,6 +30,12 @@ void launch_flux_deposit(const double *x, const double *y, const double *z, cons
                          const flux::map &m, const double *packed, const double *edges, const size_t cells, const double scale,
                          const bool is_private, const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
                          void *state, unsigned long long *counters, hipStream_t stream);
+//  The quadrature points first .. first + count of flux_label.hpp; row = numz*sub, twice_sub = (double)(2*sub).
+void launch_flux_volumes(const unsigned long long first, const size_t count, const unsigned long long row, const double twice_sub,
+                         const double area, const flux::window &window, const flux::map &m, const double *packed,
+                         const double *edges, const size_t cells, const double scale, const bool is_private,
+                         const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                         void *state, unsigned long long *counters, hipStream_t stream);
 void launch_flux_label(const double *x, const double *y, const double *z, const size_t count, const flux::map &m,
                        const double *packed, double *label, hipStream_t stream);
 

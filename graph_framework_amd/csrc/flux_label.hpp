@@ -87,6 +87,46 @@ GFHIP_HD double label_of(const map &m, const double psi) {
     return (m.flags & flag_sqrt_label) ? sqrt(s) : s;
 }
 
+//  The quadrature of the flux volumes (include/gf_hip.h): every table cell cut into sub x sub sub-cells, point
+//  (gr, gz) at the centre of sub-cell gr of numr*sub along R and gz of numz*sub along z, weighted with R times the
+//  sub-cell's area.  As above every line is one IEEE fp64 operation:
+//
+//      R = rmin + dr*((double)(2*gr + 1)/(double)(2*sub))        z = zmin + dz*((double)(2*gz + 1)/(double)(2*sub))
+//      area = (dr/sub)*(dz/sub)                                   w = R*area
+//      takes part  iff  rlo <= R && R < rhi && zlo <= z && z < zhi
+//
+//  and the label is that of (x = R, y = 0, z) by the functions above.
+struct window {
+    double rlo, rhi, zlo, zhi;
+};
+
+//  The centre of sub-cell `g` of an axis that starts at `low` with table cells of `step`; twice_sub = (double)(2*sub).
+GFHIP_HD double sub_centre(const double low, const double step, const unsigned long long g, const double twice_sub) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double fraction = static_cast<double> (2ull*g + 1ull)/twice_sub;
+    const double offset = step*fraction;
+    return low + offset;
+}
+
+GFHIP_HD double sub_area(const map &m, const uint32_t sub) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double width = m.dr/static_cast<double> (sub);
+    const double height = m.dz/static_cast<double> (sub);
+    return width*height;
+}
+
+GFHIP_HD double sub_weight(const double r, const double area) {
+    return r*area;
+}
+
+GFHIP_HD bool in_window(const window &w, const double r, const double z) {
+    return w.rlo <= r && r < w.rhi && w.zlo <= z && z < w.zhi;
+}
+
 }  // namespace flux
 }  // namespace gfhip
 

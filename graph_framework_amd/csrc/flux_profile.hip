@@ -17,6 +17,10 @@
 ///  Global path (more cells than the cap, or flag bit 1 of the map): deposits go to the global state as in
 ///  deposition.hip's deposit_kernel.  What a sample adds, the counters, the wave-level pre-sum and the atomic adds are
 ///  the functions of cell_deposit.hpp in both kernels; this one has the label and the private grid of its own.
+///
+///  flux_volume_kernel deposits the same way, but what it deposits it generates itself: the quadrature points of
+///  flux_label.hpp, weight R x area each, so that a cell's sum is the volume/2 pi of the part of the map whose label
+///  lies in the cell.  It reads no sample arrays.
 //------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,9 +58,47 @@ __device__ __forceinline__ double label_at(const flux::map &m, const double *__r
     return flux::label_of(m, flux::psi_of(c, tr, tz));
 }
 
+//  What the two deposit kernels below share.  PRIVATE: dynamic LDS = cells*67 limbs, then the cells + 1 edges; else
+//  the edges alone.  open(): the limbs zeroed and the edges staged; add(): one lane's contribution, executed by whole
+//  waves; close(): the workgroup's non-zero limbs to the global state.
+template<bool PRIVATE>
+struct workgroup_sums {
+    unsigned long long *shared;
+    unsigned int words;
+    double *staged;
+
+    __device__ __forceinline__ void open(unsigned long long *lds, const double *__restrict__ edges, const int cells) {
+        shared = lds;
+        words = PRIVATE ? static_cast<unsigned int> (cells)*superacc::limbs : 0u;
+        staged = reinterpret_cast<double *> (shared + words);
+        for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) shared[i] = 0ull;
+        for (int i = threadIdx.x; i <= cells; i += blockDim.x) staged[i] = edges[i];
+        __syncthreads();
+    }
+
+//  The private grid takes every lane's chunks as they are (ds_add_u64): the pre-sum of the global path, measured with
+//  and without it, made no difference there (DESIGN.md section 10).
+    __device__ __forceinline__ void add(unsigned long long *__restrict__ state, const deposit::contribution &a) const {
+        if constexpr (PRIVATE) {
+            deposit::add_limbs(shared, a.key, a.c0, a.c1, a.c2);
+        } else {
+            deposit::add_limbs_presummed(state, a);
+        }
+    }
+
+    __device__ __forceinline__ void close(unsigned long long *__restrict__ state) const {
+        if constexpr (PRIVATE) {
+            __syncthreads();
+            for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) {
+                const unsigned long long sum = shared[i];
+                if (sum) atomicAdd(state + i, sum);
+            }
+        }
+    }
+};
+
 }  // namespace
 
-//  PRIVATE: dynamic LDS = cells*67 limbs, then the cells + 1 edges; else the edges alone.
 //  counters: samples, outside, skipped.
 template<bool PRIVATE>
 __global__ void __launch_bounds__(private_block)
@@ -66,11 +108,8 @@ flux_deposit_kernel(const double *__restrict__ x, const double *__restrict__ y, 
                     const double *__restrict__ edges, const int cells, const double scale,
                     unsigned long long *__restrict__ state, unsigned long long *__restrict__ counters) {
     extern __shared__ unsigned long long shared[];
-    const unsigned int words = PRIVATE ? static_cast<unsigned int> (cells)*superacc::limbs : 0u;
-    double *staged = reinterpret_cast<double *> (shared + words);
-    for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) shared[i] = 0ull;
-    for (int i = threadIdx.x; i <= cells; i += blockDim.x) staged[i] = edges[i];
-    __syncthreads();
+    workgroup_sums<PRIVATE> sums;
+    sums.open(shared, edges, cells);
 
     deposit::tallies tally;
     const unsigned long long stride = static_cast<unsigned long long> (gridDim.x)*blockDim.x;
@@ -83,25 +122,58 @@ flux_deposit_kernel(const double *__restrict__ x, const double *__restrict__ y, 
         double v = 0.0;
         if (present) {
             v = value[at];
-            cell = deposit::find_cell(staged, cells, scale, label_at(m, packed, x[at], y[at], z[at]));
+            cell = deposit::find_cell(sums.staged, cells, scale, label_at(m, packed, x[at], y[at], z[at]));
         }
         const deposit::contribution a = deposit::contribution_of(cell >= 0, static_cast<unsigned int> (cell), v);
         deposit::count(tally, present, a);
-//  The private grid takes every lane's chunks as they are (ds_add_u64): the pre-sum of the global path, measured with
-//  and without it, made no difference there (DESIGN.md section 10).
-        if constexpr (PRIVATE) {
-            deposit::add_limbs(shared, a.key, a.c0, a.c1, a.c2);
-        } else {
-            deposit::add_limbs_presummed(state, a);
+        sums.add(state, a);
+    }
+    sums.close(state);
+    deposit::flush(tally, counters);
+}
+
+//  The volume quadrature of flux_label.hpp: the points first .. first + count of the flat index t = gr*row + gz
+//  (row = numz*sub sub-cells along z), generated here; nothing is read but the coefficient lines and the edges.  A lane
+//  divides once, to find the (gr, gz) of its first point, and then advances by the launch's stride, which is split
+//  into rows and a remainder once as well.  Consecutive lanes are consecutive in gz: `sub` neighbours share a
+//  coefficient line.  The shape, the counters and the sums are flux_deposit_kernel's.
+template<bool PRIVATE>
+__global__ void __launch_bounds__(private_block)
+flux_volume_kernel(const unsigned long long first, const unsigned long long count, const unsigned long long row,
+                   const double twice_sub, const double area, const flux::window window,
+                   const flux::map m, const double *__restrict__ packed,
+                   const double *__restrict__ edges, const int cells, const double scale,
+                   unsigned long long *__restrict__ state, unsigned long long *__restrict__ counters) {
+    extern __shared__ unsigned long long shared[];
+    workgroup_sums<PRIVATE> sums;
+    sums.open(shared, edges, cells);
+
+    deposit::tallies tally;
+    const unsigned long long stride = static_cast<unsigned long long> (gridDim.x)*blockDim.x;
+    const unsigned long long stride_rows = stride/row, stride_rest = stride%row;
+    const unsigned long long mine = first + static_cast<unsigned long long> (blockIdx.x)*blockDim.x + threadIdx.x;
+    unsigned long long gr = mine/row, gz = mine%row;
+    for (unsigned long long base = static_cast<unsigned long long> (blockIdx.x)*blockDim.x; base < count; base += stride) {
+        const bool present = base + threadIdx.x < count;
+        int cell = -1;
+        double w = 0.0;
+        if (present) {
+            const double r = flux::sub_centre(m.rmin, m.dr, gr, twice_sub);
+            const double z = flux::sub_centre(m.zmin, m.dz, gz, twice_sub);
+            w = flux::sub_weight(r, area);
+            if (flux::in_window(window, r, z)) cell = deposit::find_cell(sums.staged, cells, scale, label_at(m, packed, r, 0.0, z));
+        }
+        const deposit::contribution a = deposit::contribution_of(cell >= 0, static_cast<unsigned int> (cell), w);
+        deposit::count(tally, present, a);
+        sums.add(state, a);
+        gr += stride_rows;
+        gz += stride_rest;
+        if (gz >= row) {
+            gz -= row;
+            gr++;
         }
     }
-    if constexpr (PRIVATE) {
-        __syncthreads();
-        for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) {
-            const unsigned long long sum = shared[i];
-            if (sum) atomicAdd(state + i, sum);
-        }
-    }
+    sums.close(state);
     deposit::flush(tally, counters);
 }
 
@@ -138,8 +210,13 @@ void flux_launch_shape(const size_t cells, const bool allow_private, const unsig
 //  Dynamic LDS above 64 KiB has to be asked for.  The setting belongs to the function on the current device, not to a
 //  profile: always the cap's size, so that no profile lowers what another one needs.
 hipError_t flux_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *> (&flux_deposit_kernel<true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int> (private_cap_bytes));
+    for (const void *kernel : {reinterpret_cast<const void *> (&flux_deposit_kernel<true>),
+                               reinterpret_cast<const void *> (&flux_volume_kernel<true>)}) {
+        const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                      static_cast<int> (private_cap_bytes));
+        if (status != hipSuccess) return status;
+    }
+    return hipSuccess;
 }
 
 void launch_flux_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
@@ -157,6 +234,25 @@ void launch_flux_deposit(const double *x, const double *y, const double *z, cons
         hipLaunchKernelGGL(flux_deposit_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
                            static_cast<unsigned long long> (count), m, packed, edges, static_cast<int> (cells), scale,
                            static_cast<unsigned long long *> (state), counters);
+    }
+}
+
+void launch_flux_volumes(const unsigned long long first, const size_t count, const unsigned long long row, const double twice_sub,
+                         const double area, const flux::window &window, const flux::map &m, const double *packed,
+                         const double *edges, const size_t cells, const double scale, const bool is_private,
+                         const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                         void *state, unsigned long long *counters, hipStream_t stream) {
+    if (count == 0) return;
+    const size_t want = (count + block - 1)/block;
+    const unsigned int grid = static_cast<unsigned int> (want < max_workgroups ? want : max_workgroups);
+    if (is_private) {
+        hipLaunchKernelGGL(flux_volume_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, first,
+                           static_cast<unsigned long long> (count), row, twice_sub, area, window, m, packed, edges,
+                           static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
+    } else {
+        hipLaunchKernelGGL(flux_volume_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, first,
+                           static_cast<unsigned long long> (count), row, twice_sub, area, window, m, packed, edges,
+                           static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
     }
 }
 

@@ -1870,6 +1870,108 @@ extern "C" int gfhip_flux_label_host(const gfhip_flux_map *map, const double *x,
     return 0;
 }
 
+//  What a run of quadrature points needs beside the map (flux_label.hpp), or why it is refused.
+struct volume_points {
+    unsigned long long row = 0;                        // numz*sub: the sub-cells along z
+    double twice_sub = 0.0, area = 0.0;
+    gfhip::flux::window window = {};
+};
+
+static const char *volume_points_of(const gfhip::flux::map &m, const uint32_t sub, const gfhip_flux_window *window,
+                                    const uint64_t first, const uint64_t count, volume_points &p) {
+    if (sub < 1 || sub > 256) return "flux volumes: sub must be 1 to 256";
+    if (!(m.dr > 0.0) || !(m.dz > 0.0) || !(m.rmin >= 0.0)) return "flux volumes need a map with dr > 0, dz > 0 and rmin >= 0";
+//  numr*numz <= 2^31 and sub*sub <= 2^16: the total fits 64 bits with room to spare.
+    p.row = m.columns*sub;
+    const uint64_t total = static_cast<uint64_t> (m.numr)*sub*p.row;
+    if (first + count < first || first + count > total) return "flux volumes: first + count exceeds the numr*sub*numz*sub points of the map";
+    const double inf = std::numeric_limits<double>::infinity();
+    p.window = window ? gfhip::flux::window{window->rlo, window->rhi, window->zlo, window->zhi} : gfhip::flux::window{-inf, inf, -inf, inf};
+    if (!(p.window.rlo < p.window.rhi) || !(p.window.zlo < p.window.zhi)) return "flux volumes: a window needs rlo < rhi and zlo < zhi, no NaN";
+    p.twice_sub = static_cast<double> (2u*sub);
+    p.area = gfhip::flux::sub_area(m, sub);
+    return nullptr;
+}
+
+extern "C" int gfhip_flux_add_volumes(gfhip_flux *f, uint32_t sub, const gfhip_flux_window *window, uint64_t first, uint64_t count) {
+    if (!f) return 1;
+    volume_points p;
+    if (const char *refused = volume_points_of(f->map, sub, window, first, count, p)) return f->ctx->fail(refused);
+    return f->add(count, [&](const size_t done, const size_t piece) {
+        gfhip::launch_flux_volumes(first + done, piece, p.row, p.twice_sub, p.area, p.window, f->map, f->packed.get(),
+                                   f->edges.get(), f->cells, f->scale, f->is_private, f->block, f->max_workgroups,
+                                   f->lds_bytes, f->state.get(), f->counters.get(), f->ctx->stream);
+    });
+}
+
+//  Host side, no device: the quadrature and the label of flux_label.hpp and superacc.hpp's deposit on the CPU.
+extern "C" int gfhip_flux_volumes_host(const gfhip_flux_map *map, const double *edges, size_t cells, uint32_t sub,
+                                       const gfhip_flux_window *window, uint64_t first, uint64_t count,
+                                       int64_t *limbs, uint64_t counters[3]) {
+    if (!map || !edges || !limbs || !counters) {
+        creation_error = "gfhip_flux_volumes_host needs a map, edges, limbs and counters";
+        return 1;
+    }
+    if (cells < 1 || cells > flux_cell_limit) {
+        creation_error = "a flux profile has 1 to 4096 cells";
+        return 1;
+    }
+    if (!edges_increase(edges, cells)) {
+        creation_error = "the edges of a flux profile must be finite and strictly increasing";
+        return 1;
+    }
+    gfhip::flux::map m;
+    volume_points p;
+    const char *refused = flux_map_of(map, m);
+    if (!refused) refused = volume_points_of(m, sub, window, first, count, p);
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    const size_t table = static_cast<size_t> (map->numr*map->numz);
+    const auto normalise_all = [&]() {
+        for (size_t cell = 0; cell < cells; cell++) gfhip::superacc::normalise(limbs + cell*gfhip::superacc::limbs);
+    };
+    uint64_t pending = 0, outside = 0, skipped = 0;
+    unsigned long long gr = first/p.row, gz = first%p.row;
+    for (uint64_t t = 0; t < count; t++) {
+        const double r = gfhip::flux::sub_centre(m.rmin, m.dr, gr, p.twice_sub);
+        const double z = gfhip::flux::sub_centre(m.zmin, m.dz, gz, p.twice_sub);
+        if (++gz == p.row) {
+            gz = 0;
+            gr++;
+        }
+        double tr, tz, c[16];
+        const long long at = gfhip::flux::in_window(p.window, r, z) ? gfhip::flux::locate(m, r, 0.0, z, tr, tz) : -1;
+        if (at < 0) {
+            outside++;
+            continue;
+        }
+        for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
+        const double label = gfhip::flux::label_of(m, gfhip::flux::psi_of(c, tr, tz));
+        if (!(label >= edges[0] && label < edges[cells])) {
+            outside++;
+            continue;
+        }
+        const size_t cell = static_cast<size_t> (std::upper_bound(edges, edges + cells + 1, label) - edges) - 1;
+        const double w = gfhip::flux::sub_weight(r, p.area);
+        if (!gfhip::superacc::is_finite(w)) {
+            skipped++;
+            continue;
+        }
+        if (++pending > gfhip::superacc::deposits_per_normalise) {
+            normalise_all();
+            pending = 1;
+        }
+        gfhip::superacc::deposit(limbs + cell*gfhip::superacc::limbs, w);
+    }
+    normalise_all();
+    counters[0] += count;
+    counters[1] += outside;
+    counters[2] += skipped;
+    return 0;
+}
+
 //  Host side, no device: the functions of superacc.hpp that the kernels run, on one accumulator.
 extern "C" int gfhip_exact_sum(const double *values, size_t count, double *sum, int64_t *limbs) {
     if ((!values && count) || !sum) return 1;

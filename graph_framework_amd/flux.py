@@ -6,6 +6,10 @@ in the fixed arithmetic of csrc/flux_label.hpp, finds the label's cell among the
 (edge[i] <= label < edge[i+1]) and adds the value to that cell's superaccumulator (csrc/superacc.hpp).  A profile is small
 enough for every workgroup to sum its deposits in LDS before they reach memory (csrc/flux_profile.hip); the state is the
 same bytes with and without that, and for any order of samples, records, files or shards.
+
+The volume between a cell's two flux surfaces is one more deposit into the same cells, of quadrature points that the
+device generates itself (FluxProfile.add_volumes, the contract in include/gf_hip.h); volumes() and density() turn power
+per cell into power per cubic metre.
 """
 import ctypes
 import os
@@ -73,6 +77,42 @@ def label_host(tables, x, y, z, psi0=None, span=None, sqrt_label=False):
     return label
 
 
+class _Window(ctypes.Structure):
+    _fields_ = [("rlo", ctypes.c_double), ("rhi", ctypes.c_double), ("zlo", ctypes.c_double), ("zhi", ctypes.c_double)]
+
+
+def _window(window):
+    """(the pointer gfhip_flux_add_volumes takes, the structure behind it): None is the whole map."""
+    if window is None:
+        return None, None
+    given = _Window(*(float(v) for v in window))
+    return ctypes.byref(given), given
+
+
+def _point_count(tables, sub, first, count):
+    numr, numz = np.asarray(tables[TABLE_NAMES[0]]).shape
+    return numr*int(sub)*numz*int(sub) - int(first) if count is None else int(count)
+
+
+def volumes_host(tables, edges, sub, window=None, psi0=None, span=None, sqrt_label=False, first=0, count=None):
+    """The quadrature of FluxProfile.add_volumes on the CPU (gfhip_flux_volumes_host): (limbs (cells, 67), counts), the
+    bytes and numbers of a profile's state() and counts() after the same points."""
+    from . import _lib
+    lib = _lib.load()
+    given, keep = flux_map(tables, psi0, span, sqrt_label)
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    if edges.size < 2:
+        raise ValueError("a profile needs at least two edges")
+    limbs = np.zeros((edges.size - 1, LIMBS), dtype=np.int64)
+    counters = np.zeros(3, dtype=np.uint64)
+    pointer, keep_window = _window(window)
+    if lib.gfhip_flux_volumes_host(ctypes.byref(given), edges.ctypes.data, edges.size - 1, int(sub), pointer, int(first),
+                                   _point_count(tables, sub, first, count), limbs.ctypes.data, counters.ctypes.data):
+        raise GfHipError(lib.gfhip_last_error(None).decode())
+    del keep, keep_window
+    return limbs, dict(zip(("samples", "outside", "skipped"), (int(c) for c in counters)))
+
+
 class FluxProfile(ExactCells):
     """A radial profile of exact sums on a context's device (gfhip_flux_*, include/gf_hip.h); state() is (cells, 67)."""
     prefix = "flux"
@@ -111,6 +151,29 @@ class FluxProfile(ExactCells):
         self.context._check(self.lib.gfhip_flux_merge(self.handle, limbs.ctypes.data, limbs.shape[0], int(samples), int(outside),
                                                       int(skipped)))
 
+    def add_volumes(self, sub=16, window=None, first=0, count=None):
+        """Deposit the quadrature points first .. first + count (default: to the last) of include/gf_hip.h's flux
+        volumes into this profile: every table cell cut into sub x sub, weight R x area, window = (rlo, rhi, zlo, zhi) or
+        the whole map.  Asynchronous.  For callers that shard the point range over devices and merge()."""
+        pointer, keep = _window(window)
+        self.context._check(self.lib.gfhip_flux_add_volumes(self.handle, int(sub), pointer, int(first),
+                                                            _point_count(self.tables, sub, first, count)))
+        del keep
+
+    def volumes(self, sub=16, window=None, first=0, count=None):
+        """(volume[cells] in m^3, counts): 2 pi times the exact sum of R dR dz over the part of the map (or window)
+        whose label lies in each cell, on a twin of this profile.  Between closed surfaces that is the shell's volume."""
+        twin = self.like(self.context)
+        try:
+            twin.add_volumes(sub, window, first, count)
+            return twin.read()*(2.0*np.pi), twin.counts()
+        finally:
+            twin.close()
+
+    def density(self, divisor=1.0, sub=16, window=None):
+        """read(divisor)/volume per cell, dP/dV; NaN where no quadrature point reached the cell."""
+        return density_variables(self, self.read(divisor), sub, window)["density"]
+
     def info(self):
         """How deposits are launched: {private_sums, workgroup_size, cap_cells, max_workgroups, lds_bytes}."""
         info = _Info()
@@ -121,10 +184,11 @@ class FluxProfile(ExactCells):
 
 
 def flux_deposition(directory, num_files, tables, cells, low, high, psi0=None, span=None, sqrt_label=False, private=True,
-                    index=0, profile=None):
+                    index=0, profile=None, density=False, sub=16, window=None):
     """bin_deposition's counterpart on flux surfaces: d_power of result0.nc .. result<num_files - 1>.nc binned on
     `cells` uniform cells of the label between `low` and `high`, divided by the total number of rays, written to
-    <directory>/flux_bins.nc.  Returns (bins, counts).  profile: a FluxProfile that receives the exact state as well."""
+    <directory>/flux_bins.nc.  Returns (bins, counts).  profile: a FluxProfile that receives the exact state as well.
+    density: the file also gets the cells' volumes (FluxProfile.volumes(sub, window)) and bins/volume."""
     from .backend import Context
     edges = np.linspace(low, high, cells + 1)
     context = Context(index)
@@ -133,7 +197,15 @@ def flux_deposition(directory, num_files, tables, cells, low, high, psi0=None, s
     if profile is not None:
         profile.merge(local.state(), **counts)
     psi0, span, kind = local.psi0, local.span, local.label_kind
+    extra = density_variables(local, bins, sub, window) if density else {}
     local.close()
     context.close()
-    write_flux_bins(os.path.join(directory, "flux_bins.nc"), bins, edges, psi0, span, kind, **counts)
+    write_flux_bins(os.path.join(directory, "flux_bins.nc"), bins, edges, psi0, span, kind, **counts, **extra)
     return bins, counts
+
+
+def density_variables(profile, bins, sub, window=None):
+    """write_flux_bins' keywords for the power density: the volumes of `profile`'s cells and `bins` divided by them."""
+    volume, _ = profile.volumes(sub, window)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(volume=volume, density=np.where(volume == 0.0, np.nan, bins/volume), sub=sub, window=window)

@@ -358,12 +358,16 @@ class BinsFile(ResultFile):
         self.lib.H5Sclose(space)
 
     def float64_attribute(self, name, value):
-        """A global attribute of type NC_DOUBLE."""
-        space = self.lib.H5Screate(_H5S_SCALAR)
+        """A global attribute of type NC_DOUBLE: a scalar, or a sequence as a one-dimensional attribute."""
+        values = np.ascontiguousarray(value, dtype=np.float64)
+        if values.ndim:
+            space = self.lib.H5Screate_simple(1, (ctypes.c_uint64*1)(values.size), None)
+        else:
+            space = self.lib.H5Screate(_H5S_SCALAR)
         attribute = self.lib.H5Acreate2(self.file, name.encode(), self.native, space, 0, 0)
         if attribute < 0:
             raise IOError("cannot create attribute %s" % name)
-        self.lib.H5Awrite(attribute, self.native, ctypes.byref(ctypes.c_double(float(value))))
+        self.lib.H5Awrite(attribute, self.native, values.ctypes.data_as(ctypes.c_void_p))
         self.lib.H5Aclose(attribute)
         self.lib.H5Sclose(space)
 
@@ -401,10 +405,17 @@ def write_bins(path, bins, xbins, ybins, zbins, samples=0, outside=0, skipped=0)
     file.close()
 
 
-def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside=0, skipped=0):
+def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside=0, skipped=0, volume=None, density=None,
+                    sub=None, window=None):
     """flux_bins.nc, the radial counterpart of bins.nc: dimensions ns, nsp; f8 variables bins(ns), sbins(nsp), the edges
     in the label; what became of the samples as global integer attributes; psi0 and span (f8) and the label kind ("s":
-    (psi - psi0)/span, "sqrt_s": its square root) as global attributes."""
+    (psi - psi0)/span, "sqrt_s": its square root) as global attributes.  With `volume` and `density` (both or neither)
+    also the f8 variables volume(ns), the cells' volumes in m^3, and density(ns), and the quadrature they came from as
+    global attributes: sub (integer) and window (four f8: rlo, rhi, zlo, zhi; infinite where there was no window)."""
+    if (volume is None) != (density is None):
+        raise ValueError("volume and density go together")
+    if volume is not None and sub is None:
+        raise ValueError("volume and density need the sub they were computed with")
     bins = np.asarray(bins).reshape(-1)
     file = BinsFile(path)
     file.create_dimension("ns", bins.size)
@@ -415,6 +426,11 @@ def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside
     file.float64_attribute("psi0", psi0)
     file.float64_attribute("span", span)
     file.text_attribute("label", label)
+    if volume is not None:
+        file.write_variable("volume", np.asarray(volume).reshape(-1), ("ns",))
+        file.write_variable("density", np.asarray(density).reshape(-1), ("ns",))
+        file.int64_attribute("sub", sub)
+        file.float64_attribute("window", (-np.inf, np.inf, -np.inf, np.inf) if window is None else window)
     file.close()
 
 

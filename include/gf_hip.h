@@ -355,7 +355,31 @@ void gfhip_bins_destroy(gfhip_bins *bins);
  *   cells of the incoming state and refuses another shape.
  * gfhip_flux_info: how the deposits are launched.
  * gfhip_flux_label_host: no device; flux_label.hpp on the CPU, NaN where outside the map.  Errors:
- *   gfhip_last_error(NULL). */
+ *   gfhip_last_error(NULL).
+ *
+ * Flux volumes: the power density dP/dV needs the volume between a cell's two flux surfaces.  It is one more
+ * deposit into the same cells, of quadrature weights that the kernel generates itself.  The numr x numz table
+ * cells are cut into sub x sub sub-cells each, 1 <= sub <= 256; point t of the total = numr*sub * numz*sub has
+ * the sub-indices gr = t / (numz*sub) and gz = t % (numz*sub), and, every line one IEEE fp64 operation, nothing
+ * fused:
+ *     R = rmin + dr*((double)(2*gr + 1)/(double)(2*sub));  z = zmin + dz*((double)(2*gz + 1)/(double)(2*sub))
+ *     area = (dr/sub)*(dz/sub)   (once, on the host);  w = R*area
+ *     label = the label above of (x = R, y = 0, z)
+ * With a window the point takes part iff rlo <= R < rhi && zlo <= z < zhi; NULL is the whole map.  A point that
+ * takes part and whose label lies in cell i adds w to that cell.  Every point counts as a sample; one outside
+ * the window, the map or the edges, or with a NaN label, as `outside`.  The state then holds the sum of
+ * R dR dz per cell, exactly, and the volume in m^3 is 2 pi times the value read (rounded once).  That number
+ * is the volume of the part of the map (or window) whose label lies in the cell: the shell between two closed
+ * surfaces that lie inside the window; for cells beyond the last closed surface what it says and no more (a
+ * label range that covers a whole rectangular map puts the map's corners into the outer cells).
+ *
+ * gfhip_flux_add_volumes: the points first .. first + count into the profile, asynchronous; launches of at
+ *   most 2^30 points, normalised by the rule of gfhip_flux_add.  A volume profile is an ordinary profile with
+ *   the same map and edges: _state, _merge, _read and _counts as above, and shards of the point range merge.
+ *   Refused before any launch: sub outside 1-256; first + count beyond the total (or overflowing); a window
+ *   with a NaN or lo >= hi (+-inf is allowed); a map with dr <= 0, dz <= 0 or rmin < 0.
+ * gfhip_flux_volumes_host: no device, no context; the same points on the CPU with the same refusals, added to
+ *   the cells*67 `limbs` (which are then canonical) and to the three counters.  Errors: gfhip_last_error(NULL). */
 typedef struct gfhip_flux gfhip_flux;
 
 #define GFHIP_FLUX_SQRT_LABEL 1u
@@ -388,6 +412,15 @@ int gfhip_flux_info(gfhip_flux *flux, struct gfhip_flux_info *info);
 void gfhip_flux_destroy(gfhip_flux *flux);
 int gfhip_flux_label_host(const struct gfhip_flux_map *map, const double *x, const double *y, const double *z,
                           size_t count, double *label);
+
+struct gfhip_flux_window {
+    double rlo, rhi, zlo, zhi;
+};
+
+int gfhip_flux_add_volumes(gfhip_flux *flux, uint32_t sub, const struct gfhip_flux_window *window, uint64_t first, uint64_t count);
+int gfhip_flux_volumes_host(const struct gfhip_flux_map *map, const double *edges, size_t cells, uint32_t sub,
+                            const struct gfhip_flux_window *window, uint64_t first, uint64_t count,
+                            int64_t *limbs, uint64_t counters[3]);
 
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
