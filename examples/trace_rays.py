@@ -9,6 +9,7 @@ with a record every `sub_steps`, result<rank>.nc) on the MI355X backend.
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --bins 32,32,32 --bin-box 1.0,2.6,-0.4,0.4,-0.4,0.4 --one-pass
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --one-pass
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --flux-density 16 --flux-window 1.0,2.4,-1.0,1.0
+    python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 16 --flux-tables tests/golden/efit_tables.npz --npar-bins 16 --npar-range -1,1 --one-pass
     python examples/trace_rays.py --equilibrium vmec --rays 20000 --steps 10 --sub-steps 2 --output /tmp/vmec_rays
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/trace_rays.py ...
 
@@ -21,6 +22,8 @@ and the rank writes <output>_bins<rank>.nc: its own rays' sums divided by its ow
 With --flux-bins and --flux-tables (alone or next to --bins) d_power is also binned on flux surfaces
 (graph_framework_amd/flux.py) and the rank writes <output>_flux<rank>.nc; with --flux-density [SUB] (and --flux-window)
 the file also holds the cells' volumes and the power density, bins/volume.
+With --npar-bins N (and --npar-range) next to --flux-bins d_power is also binned over the flux label and the parallel
+refractive index N = c (k.B)/(|B| w) (graph_framework_amd/spectrum.py) and the rank writes <output>_spectrum<rank>.nc.
 With --one-pass as well the same work items run on every record while the trace holds it in device memory
 (graph_framework_amd/pipeline.py): same file, same bits, written once, and no pass over the file afterwards.
 """
@@ -74,10 +77,20 @@ def main():
                              "the power density bins/volume, as volume and density in <output>_flux<rank>.nc")
     parser.add_argument("--flux-window", default=None, metavar="RLO,RHI,ZLO,ZHI",
                         help="with --flux-density: only the part of the map with RLO <= R < RHI and ZLO <= z < ZHI counts as volume")
+    parser.add_argument("--npar-bins", type=int, default=None, metavar="N",
+                        help="with --flux-bins and --flux-tables: absorbed power also over N uniform cells of the parallel "
+                             "refractive index, as <output>_spectrum<rank>.nc")
+    parser.add_argument("--npar-range", default="-1,1", metavar="LOW,HIGH", help="the range of N the cells divide")
     parser.add_argument("--one-pass", action="store_true",
                         help="with --output and --absorption-model: kamp, power and the bins of every record while the rays are "
                              "traced, instead of two more passes over the file")
-    args = parser.parse_args()
+#  "--npar-range -1,1": a range that begins with a minus sign is no option; hand it over as --npar-range=-1,1
+    argv = sys.argv[1:]
+    for at in range(len(argv) - 1):
+        if argv[at] == "--npar-range":
+            argv[at:at + 2] = ["--npar-range=" + argv[at + 1]]
+            break
+    args = parser.parse_args(argv)
     if (args.bins is None) != (args.bin_box is None):
         parser.error("--bins and --bin-box go together")
     if (args.flux_bins is None) != (args.flux_tables is None):
@@ -88,6 +101,10 @@ def main():
         parser.error("--flux-density needs --flux-bins")
     if args.flux_window is not None and args.flux_density is None:
         parser.error("--flux-window needs --flux-density")
+    if args.npar_bins is not None and args.flux_bins is None:
+        parser.error("--npar-bins needs --flux-bins and --flux-tables")
+    if args.npar_range != "-1,1" and args.npar_bins is None:
+        parser.error("--npar-range needs --npar-bins")
     if args.one_pass and not (args.output and args.absorption_model):
         parser.error("--one-pass needs --output and --absorption-model")
 
@@ -155,15 +172,42 @@ def main():
         print("rank %d: flux profile on %d cells of %s: %d samples, %d outside, %d skipped; sum of bins %.6e"
               % (rank, bins.size, kind, counts["samples"], counts["outside"], counts["skipped"], float(bins.sum())))
 
+    def flux_spectrum():
+        """(context, spectrum) of --npar-bins/--npar-range on the label cells of --flux-bins."""
+        from graph_framework_amd import Context
+        from graph_framework_amd.spectrum import FluxSpectrum
+        low, high = (float(v) for v in args.flux_range.split(","))
+        npar_low, npar_high = (float(v) for v in args.npar_range.split(","))
+        tables = dict(np.load(args.flux_tables))
+        context = Context(local_rank)
+#  The tracer's w is omega/c (its dispersion relations read wpe2 + k.k - w*w), so N = k.B/(|B| w): c = 1.
+        return context, FluxSpectrum(context, tables, np.linspace(low, high, args.flux_bins + 1),
+                                     np.linspace(npar_low, npar_high, args.npar_bins + 1), sqrt_label=args.flux_sqrt, c=1.0)
+
+    def write_spectrum(context, spectrum):
+        from graph_framework_amd.output import write_spectrum_bins
+        counts = spectrum.counts()
+        bins = spectrum.read(end - begin)
+        kind = spectrum.label_kind
+        write_spectrum_bins("%s_spectrum%d.nc" % (args.output, rank), bins, spectrum.sedges, spectrum.nedges, spectrum.psi0,
+                            spectrum.span, kind, spectrum.c, **counts)
+        spectrum.close()
+        context.close()
+        print("rank %d: spectrum on %dx%d cells of %s and N: %d samples, %d outside, %d skipped; sum of bins %.6e"
+              % (rank, bins.shape[0], bins.shape[1], kind, counts["samples"], counts["outside"], counts["skipped"],
+                 float(bins.sum())))
+
     grid = None
     surfaces = None
+    waves = None
     if args.one_pass:
         from graph_framework_amd.pipeline import OnePass
         grid = deposition_grid() if args.bins else None
         surfaces = flux_profile() if args.flux_bins else None
+        waves = flux_spectrum() if args.npar_bins else None
         writer = OnePass(solve.work.context, end - begin, path, model=args.absorption_model, index=local_rank,
                          stream=solve.torch_stream.cuda_stream, deposition=grid[1] if grid else None,
-                         flux=surfaces[1] if surfaces else None)
+                         flux=surfaces[1] if surfaces else None, spectrum=waves[1] if waves else None)
         write_step = writer.record
     else:
         writer = TrajectoryWriter(solve, path) if args.output else None
@@ -197,18 +241,23 @@ def main():
                 write_deposition(*grid)
             if surfaces:
                 write_flux(*surfaces)
+            if waves:
+                write_spectrum(*waves)
         else:
             from graph_framework_amd.absorption import bin_power, run_absorption
             start = time.perf_counter()
             run_absorption(path, records, index=local_rank, model=args.absorption_model)
             grid = deposition_grid() if args.bins else None
             surfaces = flux_profile() if args.flux_bins else None
+            waves = flux_spectrum() if args.npar_bins else None
             bin_power(path, records, index=local_rank, deposition=grid[1] if grid else None,
-                      flux=surfaces[1] if surfaces else None)
+                      flux=surfaces[1] if surfaces else None, spectrum=waves[1] if waves else None)
             if grid:
                 write_deposition(*grid)
             if surfaces:
                 write_flux(*surfaces)
+            if waves:
+                write_spectrum(*waves)
         elapsed = time.perf_counter() - start
         result = ResultFile(path)
         power = result.read("power", records)

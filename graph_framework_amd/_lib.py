@@ -100,6 +100,16 @@ SYMBOLS = [
     ("gfhip_flux_label_host", _I, [_P, _P, _P, _P, _S, _P]),
     ("gfhip_flux_add_volumes", _I, [_P, _U32, _P, _U64, _U64]),
     ("gfhip_flux_volumes_host", _I, [_P, _P, _S, _U32, _P, _U64, _U64, _P, _P]),
+    ("gfhip_spectrum_create", _P, [_P, _P, _P, _P, _S, _P, _S]),
+    ("gfhip_spectrum_add", _I, [_P, _P, _S]),
+    ("gfhip_spectrum_npar", _I, [_P, _P, _U64, _U64, _S]),
+    ("gfhip_spectrum_counts", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("gfhip_spectrum_state", _I, [_P, _P]),
+    ("gfhip_spectrum_merge", _I, [_P, _P, _S, _S, _U64, _U64, _U64]),
+    ("gfhip_spectrum_read", _I, [_P, ctypes.c_double, _P]),
+    ("gfhip_spectrum_info", _I, [_P, _P]),
+    ("gfhip_spectrum_destroy", None, [_P]),
+    ("gfhip_spectrum_npar_host", _I, [_P, _P, _P, _S, _P, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 

@@ -144,7 +144,19 @@ def run_absorption(filename, num_steps, index=0, model="weak_damping"):
     return power
 
 
-def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=None, flux=None):
+#  what a spectrum.FluxSpectrum reads of a record beside x, y, z and d_power
+WAVE_NAMES = ("kx", "ky", "kz", "w")
+
+
+def allocate_wave_buffers(context, num_rays):
+    """fp64 buffers kx, ky, kz, w of `num_rays` elements in a power stage's context, for a spectrum's deposits."""
+    from . import _lib
+    from .backend import key_of
+    for name in WAVE_NAMES:
+        context._check(context.lib.gfhip_allocate_buffer(context.handle, key_of(name), num_rays, _lib.GFIR_F64))
+
+
+def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=None, flux=None, spectrum=None):
     """bin_power's per-shard body (xrays.cpp:694-786).
 
     deposition: a deposition.Deposition (on any context).  Every record's x, y, z and d_power are then binned on
@@ -152,7 +164,9 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
     deposition.bin_deposition would find in the file afterwards, record 0 (d_power = 0) included, without a second
     pass over it — and the exact state is merged into `deposition` at the end.
     flux: a flux.FluxProfile (on any context), alone or next to `deposition`: the same records binned on its flux
-    surfaces, the exact state merged into it at the end."""
+    surfaces, the exact state merged into it at the end.
+    spectrum: a spectrum.FluxSpectrum (on any context), alone or next to the others: the same records binned over the
+    flux label and N, with kx, ky, kz and w of every record uploaded from the file next to x, y, z."""
     file = ResultFile(filename)
     n = file.num_rays
     work, host, item = power_work(n, index, stream, item)
@@ -167,11 +181,23 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
         host[name + "_last"][:] = host[name]
 #  (the caller's, its local twin on this context)
     grids = [(target, target.like(work.context)) for target in (deposition, flux) if target is not None]
-    if grids:
+    spectra = [(spectrum, spectrum.like(work.context))] if spectrum is not None else []
+    if spectra:
+        allocate_wave_buffers(work.context, n)
+
+    def feed(record):
+        """The record's deposits, right behind d_power on the context's stream."""
+        for _, local in grids:
+            local.add("x", "y", "z", "d_power", n)
+        for _, local in spectra:
+            for name in WAVE_NAMES:
+                work.context.copy_to_device(name, file.read(name, record))
+            local.add("x", "y", "z", *WAVE_NAMES, "d_power", n)
+
+    if grids or spectra:
         for name in ("x", "y", "z"):
             work.copy_to_device(name, host[name])
-    for _, local in grids:
-        local.add("x", "y", "z", "d_power", n)
+    feed(0)
     work.wait()                                                             # mirrors hold the initial values
     file.write({"power": power.copy(), "d_power": d_power.copy()}, index=0)
     sync = _Writer()
@@ -184,15 +210,14 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
         host["kamp"][:] = file.read("kamp", j, part=1)                      # reference_imag_variable
         work.copy_to_device("kamp", host["kamp"])
         work.run()
-        for _, local in grids:
-            local.add("x", "y", "z", "d_power", n)
+        feed(j)
         sync.join()
         work.wait()
         record = {"power": power.copy(), "d_power": d_power.copy()}
         sync.start(lambda record=record, j=j: file.write(record, index=j))
     sync.join()
     file.close()
-    for target, local in grids:
+    for target, local in grids + spectra:
         target.merge(local.state(), **local.counts())
         local.close()
     work.context.close()

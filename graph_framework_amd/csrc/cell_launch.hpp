@@ -1,6 +1,6 @@
 //------------------------------------------------------------------------------
 ///  @file cell_launch.hpp
-///  @brief What gf_hip.cpp launches of deposition.hip and flux_profile.hip.
+///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip and flux_spectrum.hip.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_CELL_LAUNCH_HPP
 #define GFHIP_CELL_LAUNCH_HPP
@@ -22,8 +22,9 @@ void launch_deposit(const double *x, const double *y, const double *z, const dou
                     const double *edges, const int nx, const int ny, const int nz, const double *scale,
                     void *state, unsigned long long *counters, const unsigned int num_cus, hipStream_t stream);
 
-//  flux_profile.hip.  The shape of a profile's deposit launches, decided once per profile.
-void flux_launch_shape(const size_t cells, const bool allow_private, const unsigned int num_cus,
+//  flux_profile.hip.  The shape of the deposit launches of a profile or a spectrum, decided once per object;
+//  edge_count: the edges staged in LDS (a profile's cells + 1, a spectrum's two axes).
+void flux_launch_shape(const size_t cells, const size_t edge_count, const bool allow_private, const unsigned int num_cus,
                        bool *is_private, size_t *cap, unsigned int *block, size_t *max_workgroups, size_t *lds_bytes);
 hipError_t flux_prepare();
 void launch_flux_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
@@ -38,6 +39,17 @@ void launch_flux_volumes(const unsigned long long first, const size_t count, con
                          void *state, unsigned long long *counters, hipStream_t stream);
 void launch_flux_label(const double *x, const double *y, const double *z, const size_t count, const flux::map &m,
                        const double *packed, double *label, hipStream_t stream);
+
+//  flux_spectrum.hip.  columns: x, y, z, kx, ky, kz, w (and the value, for the deposit); fpol: [interval][4]; edges: the
+//  ns + 1 of the label, then the nn + 1 of N; the cell of (is, in) is is*nn + in.
+hipError_t spectrum_prepare();
+void launch_spectrum_deposit(const double *const *columns, const size_t first, const size_t count, const flux::map &m,
+                             const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                             const size_t ns, const size_t nn, const double sscale, const double nscale, const bool is_private,
+                             const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                             void *state, unsigned long long *counters, hipStream_t stream);
+void launch_spectrum_npar(const double *const *columns, const size_t count, const flux::map &m, const flux::field &f,
+                          const double *packed, const double *fpol, double *label, double *npar, hipStream_t stream);
 
 }  // namespace gfhip
 

@@ -18,6 +18,27 @@
 ///      label = s, or sqrt(s) when flag bit 0 is set (s < 0 gives NaN)
 ///
 ///  Unlike the tracer's gather the map does not clamp: a point off the table has no label (NaN).  Plain C++.
+///
+///  The field direction and the parallel refractive index N = c (k.B)/(|B| w) of a sample (x, y, z, kx, ky, kz, w),
+///  by the same rules, for flux_spectrum.hip.  B = (psi_z/R, fpol/R, -psi_R/R) in (R, phi, z), the common 1/R dropped;
+///  fpol is a cubic in the GLOBAL normalised tp per interval of the psi table, the interval clamped as the tracer's
+///  1-D gather clamps it (labels a little above 1 occur inside the map); c[a][b], col_a and psi are those above:
+///
+///      dcol_a = ((c[a][3]*3.0)*tz + c[a][2]*2.0)*tz + c[a][1]                 a = 0..3
+///      psi_tz = ((dcol_3*tr + dcol_2)*tr + dcol_1)*tr + dcol_0
+///      psi_tr = ((col_3*3.0)*tr + col_2*2.0)*tr + col_1
+///      gR = psi_tr/dr                 gZ = psi_tz/dz
+///      tp = (psi - psimin)/dpsi
+///      q  = 0 unless tp >= 0 (a NaN gives 0);  numpsi - 1 if tp >= numpsi;  else (int)tp
+///      f  = ((fpol_c3[q]*tp + fpol_c2[q])*tp + fpol_c1[q])*tp + fpol_c0[q]
+///      a  = kx*x + ky*y               b = ky*x - kx*y
+///      num  = (a*gZ + b*f)/R - kz*gR
+///      den  = sqrt((gZ*gZ + f*f) + gR*gR)
+///      npar = (c*(num/den))/w
+///
+///  No integer conversion of a NaN or of a value out of range is reached.  Which NaN an operation gives is not IEEE's
+///  business and differs between processors: the label and npar of a sample leave as canonical(), so that the bits are
+///  the same everywhere.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_FLUX_LABEL_HPP
 #define GFHIP_FLUX_LABEL_HPP
@@ -43,26 +64,33 @@ struct map {
     uint32_t flags;
 };
 
-//  The table cell of (x, y, z), i*numz + j, with the normalised coordinates it was found from; -1 outside the map.
-GFHIP_HD long long locate(const map &m, const double x, const double y, const double z, double &tr, double &tz) {
+//  R of (x, y).
+GFHIP_HD double radius_of(const double x, const double y) {
 #ifdef __clang__
 #pragma clang fp contract(off)
 #endif
     const double xx = x*x;
     const double yy = y*y;
-    const double r = sqrt(xx + yy);
+    return sqrt(xx + yy);
+}
+
+//  The table cell of (x, y, z), i*numz + j, with the normalised coordinates it was found from; -1 outside the map.
+GFHIP_HD long long locate(const map &m, const double x, const double y, const double z, double &tr, double &tz) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double r = radius_of(x, y);
     tr = (r - m.rmin)/m.dr;
     tz = (z - m.zmin)/m.dz;
     if (!(tr >= 0.0 && tr < m.numr && tz >= 0.0 && tz < m.numz)) return -1;
     return static_cast<long long> (static_cast<int> (tr))*static_cast<long long> (m.columns) + static_cast<int> (tz);
 }
 
-//  psi from a cell's 16 coefficients, c[a*4 + b].
-GFHIP_HD double psi_of(const double *c, const double tr, const double tz) {
+//  col_a from a cell's 16 coefficients, c[a*4 + b].
+GFHIP_HD void columns_of(const double *c, const double tz, double *column) {
 #ifdef __clang__
 #pragma clang fp contract(off)
 #endif
-    double column[4];
     for (int a = 0; a < 4; a++) {
         double t = c[4*a + 3]*tz;
         t = t + c[4*a + 2];
@@ -71,6 +99,13 @@ GFHIP_HD double psi_of(const double *c, const double tr, const double tz) {
         t = t*tz;
         column[a] = t + c[4*a];
     }
+}
+
+//  psi from the four col_a.
+GFHIP_HD double psi_from(const double *column, const double tr) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
     double p = column[3]*tr;
     p = p + column[2];
     p = p*tr;
@@ -79,12 +114,108 @@ GFHIP_HD double psi_of(const double *c, const double tr, const double tz) {
     return p + column[0];
 }
 
+//  psi from a cell's 16 coefficients, c[a*4 + b].
+GFHIP_HD double psi_of(const double *c, const double tr, const double tz) {
+    double column[4];
+    columns_of(c, tz, column);
+    return psi_from(column, tr);
+}
+
 GFHIP_HD double label_of(const map &m, const double psi) {
 #ifdef __clang__
 #pragma clang fp contract(off)
 #endif
     const double s = (psi - m.psi0)/m.span;
     return (m.flags & flag_sqrt_label) ? sqrt(s) : s;
+}
+
+//  What N needs beside the map; the fpol coefficients travel separately (four tables on the host, [q][4] on the device).
+struct field {
+    double psimin, dpsi;
+    double numpsi;                                     // the table's extent as a double: what tp is compared with
+    int last;                                          // numpsi - 1
+    double c;
+};
+
+//  psi and its derivatives along R and z at a point inside the map, from the cell's 16 coefficients.
+GFHIP_HD double psi_gradient(const map &m, const double *c, const double tr, const double tz, double &gr, double &gz) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double column[4], slope[4];
+    columns_of(c, tz, column);
+    for (int a = 0; a < 4; a++) {
+        double t = c[4*a + 3]*3.0;
+        t = t*tz;
+        const double u = c[4*a + 2]*2.0;
+        t = t + u;
+        t = t*tz;
+        slope[a] = t + c[4*a + 1];
+    }
+    const double psi_tz = psi_from(slope, tr);
+    double t = column[3]*3.0;
+    t = t*tr;
+    const double u = column[2]*2.0;
+    t = t + u;
+    t = t*tr;
+    const double psi_tr = t + column[1];
+    gr = psi_tr/m.dr;
+    gz = psi_tz/m.dz;
+    return psi_from(column, tr);
+}
+
+//  The interval q of the fpol table and the coordinate tp it is evaluated at.
+GFHIP_HD int fpol_interval(const field &f, const double psi, double &tp) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    tp = (psi - f.psimin)/f.dpsi;
+    if (!(tp >= 0.0)) return 0;
+    if (tp >= f.numpsi) return f.last;
+    return static_cast<int> (tp);
+}
+
+//  fpol from an interval's four coefficients, c0 .. c3.
+GFHIP_HD double fpol_of(const double *c, const double tp) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double f = c[3]*tp;
+    f = f + c[2];
+    f = f*tp;
+    f = f + c[1];
+    f = f*tp;
+    return f + c[0];
+}
+
+//  A NaN as the quiet NaN with no payload, 0x7ff8000000000000; every other value as it is.
+GFHIP_HD double canonical(const double v) {
+    return v == v ? v : __builtin_nan("");
+}
+
+//  N from the pieces above.
+GFHIP_HD double npar_of(const field &f, const double x, const double y, const double r, const double kx, const double ky,
+                        const double kz, const double w, const double gr, const double gz, const double fpol) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double kxx = kx*x;
+    const double kyy = ky*y;
+    const double a = kxx + kyy;
+    const double kyx = ky*x;
+    const double kxy = kx*y;
+    const double b = kyx - kxy;
+    const double agz = a*gz;
+    const double bf = b*fpol;
+    const double along = (agz + bf)/r;
+    const double kzgr = kz*gr;
+    const double num = along - kzgr;
+    const double gzgz = gz*gz;
+    const double ff = fpol*fpol;
+    const double grgr = gr*gr;
+    const double den = sqrt((gzgz + ff) + grgr);
+    const double cosine = num/den;
+    return canonical((f.c*cosine)/w);
 }
 
 //  The quadrature of the flux volumes (include/gf_hip.h): every table cell cut into sub x sub sub-cells, point

@@ -28,74 +28,17 @@
 #include "cell_deposit.hpp"
 #include "cell_launch.hpp"
 #include "flux_label.hpp"
+#include "flux_sums.hpp"
 #include "superacc.hpp"
 
 namespace gfhip {
 
+using namespace sums;                                  // flux_sums.hpp: label_at, workgroup_sums, the blocks and the cap
+
 namespace {
 
-constexpr unsigned int private_block = 1024;           // 16 waves: one workgroup per CU at the cap still has 4 waves per SIMD
-constexpr unsigned int global_block = 256;
-constexpr size_t lds_per_workgroup = 160u*1024u;
-constexpr size_t private_cap = 256;                    // cells: 256*536 + 257*8 = 139,272 B of the 163,840 a workgroup may declare
-constexpr size_t private_cap_bytes = private_cap*superacc::limbs*sizeof(unsigned long long) + (private_cap + 1)*sizeof(double);
+constexpr size_t private_cap_bytes = private_cap*bytes_per_cell + (private_cap + 1)*sizeof(double);
 static_assert(private_cap_bytes <= lds_per_workgroup, "the cap fits one workgroup's LDS");
-
-//  The label of one point, NaN outside the map.  `packed`: [table cell][16], 16-byte aligned.
-__device__ __forceinline__ double label_at(const flux::map &m, const double *__restrict__ packed,
-                                           const double x, const double y, const double z) {
-    double tr, tz;
-    const long long at = flux::locate(m, x, y, z, tr, tz);
-    if (at < 0) return __builtin_nan("");
-    const double2 *line = reinterpret_cast<const double2 *> (packed) + at*8;
-    double c[16];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const double2 pair = line[k];
-        c[2*k] = pair.x;
-        c[2*k + 1] = pair.y;
-    }
-    return flux::label_of(m, flux::psi_of(c, tr, tz));
-}
-
-//  What the two deposit kernels below share.  PRIVATE: dynamic LDS = cells*67 limbs, then the cells + 1 edges; else
-//  the edges alone.  open(): the limbs zeroed and the edges staged; add(): one lane's contribution, executed by whole
-//  waves; close(): the workgroup's non-zero limbs to the global state.
-template<bool PRIVATE>
-struct workgroup_sums {
-    unsigned long long *shared;
-    unsigned int words;
-    double *staged;
-
-    __device__ __forceinline__ void open(unsigned long long *lds, const double *__restrict__ edges, const int cells) {
-        shared = lds;
-        words = PRIVATE ? static_cast<unsigned int> (cells)*superacc::limbs : 0u;
-        staged = reinterpret_cast<double *> (shared + words);
-        for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) shared[i] = 0ull;
-        for (int i = threadIdx.x; i <= cells; i += blockDim.x) staged[i] = edges[i];
-        __syncthreads();
-    }
-
-//  The private grid takes every lane's chunks as they are (ds_add_u64): the pre-sum of the global path, measured with
-//  and without it, made no difference there.
-    __device__ __forceinline__ void add(unsigned long long *__restrict__ state, const deposit::contribution &a) const {
-        if constexpr (PRIVATE) {
-            deposit::add_limbs(shared, a.key, a.c0, a.c1, a.c2);
-        } else {
-            deposit::add_limbs_presummed(state, a);
-        }
-    }
-
-    __device__ __forceinline__ void close(unsigned long long *__restrict__ state) const {
-        if constexpr (PRIVATE) {
-            __syncthreads();
-            for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) {
-                const unsigned long long sum = shared[i];
-                if (sum) atomicAdd(state + i, sum);
-            }
-        }
-    }
-};
 
 }  // namespace
 
@@ -186,16 +129,16 @@ flux_label_kernel(const double *__restrict__ x, const double *__restrict__ y, co
     if (at < count) label[at] = label_at(m, packed, x[at], y[at], z[at]);
 }
 
-//  The shape of a profile's deposit launches.  The private path is taken when the grid and the edges fit the LDS of
-//  one workgroup and the caller has not switched it off; `cap` is the most cells it takes.
-void flux_launch_shape(const size_t cells, const bool allow_private, const unsigned int num_cus,
+//  The shape of the deposit launches of a profile (cells + 1 edges) or a spectrum (its two axes' edges).  The private
+//  path is taken when the grid and the edges fit the LDS of one workgroup and the caller has not switched it off; `cap`
+//  is the most cells it takes.
+void flux_launch_shape(const size_t cells, const size_t edge_count, const bool allow_private, const unsigned int num_cus,
                        bool *is_private, size_t *cap, unsigned int *block, size_t *max_workgroups, size_t *lds_bytes) {
-    const size_t per_cell = superacc::limbs*sizeof(unsigned long long);
     *cap = private_cap;
-    const size_t edge_bytes = (cells + 1)*sizeof(double);
-    *is_private = allow_private && cells <= *cap;
+    const size_t edge_bytes = edge_count*sizeof(double);
+    *is_private = allow_private && cells <= *cap && cells*bytes_per_cell + edge_bytes <= lds_per_workgroup;
     if (*is_private) {
-        *lds_bytes = cells*per_cell + edge_bytes;
+        *lds_bytes = cells*bytes_per_cell + edge_bytes;
         *block = private_block;
 //  Two workgroups of 1024 are all the waves a CU holds; large grids leave room for one.
         const size_t per_cu = lds_per_workgroup/(*lds_bytes) >= 2 ? 2 : 1;

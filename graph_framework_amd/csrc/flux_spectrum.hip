@@ -1,0 +1,149 @@
+//------------------------------------------------------------------------------
+///  @file flux_spectrum.hip
+///  @brief Binning of per-sample values over the flux label and the parallel refractive index, exact sums (hand-written,
+///  gfx950).
+///
+///  A sample (x, y, z, kx, ky, kz, w, value), eight fp64 reads, gets the label and N = c (k.B)/(|B| w) of
+///  flux_label.hpp: psi and its two derivatives from the cell's 16 coefficients (the [cell][16] line of
+///  flux_profile.hip), fpol from the interval's four ([q][4], one 32-byte line).  It belongs to cell (is, in) iff
+///  sedge[is] <= label < sedge[is+1] and nedge[in] <= N < nedge[in+1], both by cell_deposit.hpp's find_cell; the cells
+///  are ns*nn superaccumulators, flat index is*nn + in.
+///
+///  The sums are flux_sums.hpp's: up to 256 cells every workgroup owns the grid in LDS, the two axes' edges staged
+///  behind it; above that, or with the map's no-private flag, deposits go to the global state behind the wave pre-sum.
+///  The state does not depend on the route, the launch shape or the order of the samples.
+//------------------------------------------------------------------------------
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "cell_deposit.hpp"
+#include "cell_launch.hpp"
+#include "flux_label.hpp"
+#include "flux_sums.hpp"
+#include "superacc.hpp"
+
+namespace gfhip {
+
+using namespace sums;
+
+namespace {
+
+//  The most edges of the private path's two axes: ns*nn <= 256 gives ns + nn <= 257.
+constexpr size_t private_cap_bytes = private_cap*bytes_per_cell + (private_cap + 3)*sizeof(double);
+static_assert(private_cap_bytes <= lds_per_workgroup, "the cap fits one workgroup's LDS");
+
+//  The label and N of one sample, both NaN outside the map.  `fpol`: [interval][4], 32-byte aligned.
+__device__ __forceinline__ double npar_at(const flux::map &m, const flux::field &f, const double *__restrict__ packed,
+                                          const double *__restrict__ fpol, const double x, const double y, const double z,
+                                          const double kx, const double ky, const double kz, const double w, double &label) {
+    double tr, tz;
+    const long long at = flux::locate(m, x, y, z, tr, tz);
+    if (at < 0) {
+        label = __builtin_nan("");
+        return __builtin_nan("");
+    }
+    double c[16];
+    coefficients_at(packed, at, c);
+    double gr, gz, tp;
+    const double psi = flux::psi_gradient(m, c, tr, tz, gr, gz);
+    label = flux::canonical(flux::label_of(m, psi));
+    const int q = flux::fpol_interval(f, psi, tp);
+    const double2 *line = reinterpret_cast<const double2 *> (fpol) + static_cast<size_t> (q)*2;
+    const double2 low = line[0], high = line[1];
+    const double cubic[4] = {low.x, low.y, high.x, high.y};
+    return flux::npar_of(f, x, y, flux::radius_of(x, y), kx, ky, kz, w, gr, gz, flux::fpol_of(cubic, tp));
+}
+
+}  // namespace
+
+struct spectrum_columns {
+    const double *x, *y, *z, *kx, *ky, *kz, *w, *value;
+};
+
+//  counters: samples, outside, skipped.  edges: the ns + 1 of the label, then the nn + 1 of N.
+template<bool PRIVATE>
+__global__ void __launch_bounds__(private_block)
+spectrum_deposit_kernel(const spectrum_columns in, const unsigned long long count,
+                        const flux::map m, const flux::field f, const double *__restrict__ packed,
+                        const double *__restrict__ fpol, const double *__restrict__ edges, const int ns, const int nn,
+                        const double sscale, const double nscale,
+                        unsigned long long *__restrict__ state, unsigned long long *__restrict__ counters) {
+    extern __shared__ unsigned long long shared[];
+    workgroup_sums<PRIVATE> sums;
+    sums.open(shared, edges, ns*nn, ns + nn + 2);
+    const double *sedge = sums.staged, *nedge = sums.staged + ns + 1;
+
+    deposit::tallies tally;
+    const unsigned long long stride = static_cast<unsigned long long> (gridDim.x)*blockDim.x;
+//  `base` is the same for every lane of the workgroup: the ballots and shuffles below are executed by whole waves, and
+//  every wave of the workgroup arrives at the barrier before the flush.
+    for (unsigned long long base = static_cast<unsigned long long> (blockIdx.x)*blockDim.x; base < count; base += stride) {
+        const unsigned long long at = base + threadIdx.x;
+        const bool present = at < count;
+        int cell = -1;                                 // outside, as in the lanes past the end
+        double v = 0.0;
+        if (present) {
+            v = in.value[at];
+            double label;
+            const double npar = npar_at(m, f, packed, fpol, in.x[at], in.y[at], in.z[at], in.kx[at], in.ky[at], in.kz[at],
+                                        in.w[at], label);
+            const int is = deposit::find_cell(sedge, ns, sscale, label);
+            const int in_n = deposit::find_cell(nedge, nn, nscale, npar);
+            if (is >= 0 && in_n >= 0) cell = is*nn + in_n;
+        }
+        const deposit::contribution a = deposit::contribution_of(cell >= 0, static_cast<unsigned int> (cell), v);
+        deposit::count(tally, present, a);
+        sums.add(state, a);
+    }
+    sums.close(state);
+    deposit::flush(tally, counters);
+}
+
+//  One lane per point: its label and its N, NaN outside the map.
+__global__ void __launch_bounds__(256)
+spectrum_npar_kernel(const spectrum_columns in, const unsigned long long count, const flux::map m, const flux::field f,
+                     const double *__restrict__ packed, const double *__restrict__ fpol,
+                     double *__restrict__ label, double *__restrict__ npar) {
+    const unsigned long long at = static_cast<unsigned long long> (blockIdx.x)*blockDim.x + threadIdx.x;
+    if (at < count) {
+        double s;
+        npar[at] = npar_at(m, f, packed, fpol, in.x[at], in.y[at], in.z[at], in.kx[at], in.ky[at], in.kz[at], in.w[at], s);
+        label[at] = s;
+    }
+}
+
+//  Dynamic LDS above 64 KiB has to be asked for: always the cap's size, as flux_prepare does.
+hipError_t spectrum_prepare() {
+    return hipFuncSetAttribute(reinterpret_cast<const void *> (&spectrum_deposit_kernel<true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int> (private_cap_bytes));
+}
+
+void launch_spectrum_deposit(const double *const *columns, const size_t first, const size_t count, const flux::map &m,
+                             const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                             const size_t ns, const size_t nn, const double sscale, const double nscale, const bool is_private,
+                             const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                             void *state, unsigned long long *counters, hipStream_t stream) {
+    if (count == 0) return;
+    const spectrum_columns in = {columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first,
+                                 columns[4] + first, columns[5] + first, columns[6] + first, columns[7] + first};
+    const unsigned int grid = grid_of(count, block, max_workgroups);
+    if (is_private) {
+        hipLaunchKernelGGL(spectrum_deposit_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), m, f, packed, fpol, edges, static_cast<int> (ns),
+                           static_cast<int> (nn), sscale, nscale, static_cast<unsigned long long *> (state), counters);
+    } else {
+        hipLaunchKernelGGL(spectrum_deposit_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), m, f, packed, fpol, edges, static_cast<int> (ns),
+                           static_cast<int> (nn), sscale, nscale, static_cast<unsigned long long *> (state), counters);
+    }
+}
+
+void launch_spectrum_npar(const double *const *columns, const size_t count, const flux::map &m, const flux::field &f,
+                          const double *packed, const double *fpol, double *label, double *npar, hipStream_t stream) {
+    if (count == 0) return;
+    const spectrum_columns in = {columns[0], columns[1], columns[2], columns[3], columns[4], columns[5], columns[6], nullptr};
+    hipLaunchKernelGGL(spectrum_npar_kernel, dim3(static_cast<unsigned int> ((count + 255)/256)), dim3(256), 0, stream, in,
+                       static_cast<unsigned long long> (count), m, f, packed, fpol, label, npar);
+}
+
+}  // namespace gfhip

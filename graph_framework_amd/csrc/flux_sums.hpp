@@ -1,0 +1,101 @@
+//------------------------------------------------------------------------------
+///  @file flux_sums.hpp
+///  @brief What the deposit kernels of flux_profile.hip and flux_spectrum.hip share (device side): the label of a point
+///  from the repacked psi tables, and a workgroup's sums, private in LDS or global.
+//------------------------------------------------------------------------------
+#ifndef GFHIP_FLUX_SUMS_HPP
+#define GFHIP_FLUX_SUMS_HPP
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "cell_deposit.hpp"
+#include "flux_label.hpp"
+#include "superacc.hpp"
+
+namespace gfhip {
+namespace sums {
+
+constexpr unsigned int private_block = 1024;           // 16 waves: one workgroup per CU at the cap still has 4 waves per SIMD
+constexpr unsigned int global_block = 256;
+constexpr size_t lds_per_workgroup = 160u*1024u;
+constexpr size_t private_cap = 256;                    // cells: 256*536 + 257*8 = 139,272 B of the 163,840 a workgroup may declare
+constexpr size_t bytes_per_cell = superacc::limbs*sizeof(unsigned long long);
+
+//  A cell's 16 coefficients.  `packed`: [table cell][16], 16-byte aligned.
+__device__ __forceinline__ void coefficients_at(const double *__restrict__ packed, const long long at, double *c) {
+    const double2 *line = reinterpret_cast<const double2 *> (packed) + at*8;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const double2 pair = line[k];
+        c[2*k] = pair.x;
+        c[2*k + 1] = pair.y;
+    }
+}
+
+//  The label of one point, NaN outside the map.
+__device__ __forceinline__ double label_at(const flux::map &m, const double *__restrict__ packed,
+                                           const double x, const double y, const double z) {
+    double tr, tz;
+    const long long at = flux::locate(m, x, y, z, tr, tz);
+    if (at < 0) return __builtin_nan("");
+    double c[16];
+    coefficients_at(packed, at, c);
+    return flux::label_of(m, flux::psi_of(c, tr, tz));
+}
+
+//  What the deposit kernels share.  PRIVATE: dynamic LDS = cells*67 limbs, then the staged edges; else the edges
+//  alone.  open(): the limbs zeroed and the edges staged; add(): one lane's contribution, executed by whole waves;
+//  close(): the workgroup's non-zero limbs to the global state.
+template<bool PRIVATE>
+struct workgroup_sums {
+    unsigned long long *shared;
+    unsigned int words;
+    double *staged;
+
+//  `edge_count` edges behind the limbs: a profile's cells + 1, or a spectrum's two axes one after the other.
+    __device__ __forceinline__ void open(unsigned long long *lds, const double *__restrict__ edges, const int cells,
+                                         const int edge_count) {
+        shared = lds;
+        words = PRIVATE ? static_cast<unsigned int> (cells)*superacc::limbs : 0u;
+        staged = reinterpret_cast<double *> (shared + words);
+        for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) shared[i] = 0ull;
+        for (int i = threadIdx.x; i < edge_count; i += blockDim.x) staged[i] = edges[i];
+        __syncthreads();
+    }
+
+    __device__ __forceinline__ void open(unsigned long long *lds, const double *__restrict__ edges, const int cells) {
+        open(lds, edges, cells, cells + 1);
+    }
+
+//  The private grid takes every lane's chunks as they are (ds_add_u64): the pre-sum of the global path, measured with
+//  and without it, made no difference there.
+    __device__ __forceinline__ void add(unsigned long long *__restrict__ state, const deposit::contribution &a) const {
+        if constexpr (PRIVATE) {
+            deposit::add_limbs(shared, a.key, a.c0, a.c1, a.c2);
+        } else {
+            deposit::add_limbs_presummed(state, a);
+        }
+    }
+
+    __device__ __forceinline__ void close(unsigned long long *__restrict__ state) const {
+        if constexpr (PRIVATE) {
+            __syncthreads();
+            for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) {
+                const unsigned long long sum = shared[i];
+                if (sum) atomicAdd(state + i, sum);
+            }
+        }
+    }
+};
+
+//  The workgroups of a launch of `count` samples.
+inline unsigned int grid_of(const size_t count, const unsigned int block, const size_t max_workgroups) {
+    const size_t want = (count + block - 1)/block;
+    return static_cast<unsigned int> (want < max_workgroups ? want : max_workgroups);
+}
+
+}  // namespace sums
+}  // namespace gfhip
+
+#endif

@@ -138,6 +138,7 @@ struct gfhip_context {
     std::vector<std::unique_ptr<gfhip_kernel>> kernels;
     std::vector<std::unique_ptr<gfhip_bins>> bins;     // deposition grids (gfhip_bins_create), until gfhip_bins_destroy
     std::vector<std::unique_ptr<gfhip_flux>> fluxes;   // flux profiles (gfhip_flux_create), until gfhip_flux_destroy
+    std::vector<std::unique_ptr<gfhip_spectrum>> spectra;      // spectra (gfhip_spectrum_create), until gfhip_spectrum_destroy
     std::string error;
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
@@ -226,14 +227,31 @@ struct gfhip_bins : exact_cells {
     device_ptr<double> edges;                          // the three axes' edges one after the other
 };
 
-//  A flux-surface profile; the psi tables as [table cell][16].
-struct gfhip_flux : exact_cells {
+//  What a flux-surface profile and a spectrum share: the map, the psi tables as [table cell][16], the edges the
+//  deposit kernel stages in LDS and the shape of its launches.
+struct flux_cells : exact_cells {
     gfhip::flux::map map = {};
-    double scale = 0.0;                                // cells/(last edge - first edge)
     device_ptr<double> packed, edges;
     bool is_private = false;
     size_t cap = 0, max_workgroups = 0, lds_bytes = 0;
     unsigned int block = 0;
+
+    int create(gfhip_context *context, const gfhip_flux_map *given, size_t count, const std::vector<double> &all_edges,
+               hipError_t (*prepare)());
+    void info_to(struct gfhip_flux_info *info) const;
+};
+
+//  A flux-surface profile.
+struct gfhip_flux : flux_cells {
+    double scale = 0.0;                                // cells/(last edge - first edge)
+};
+
+//  A spectrum over the flux label and N: cell is*nn + in; the edges of the label, then those of N; fpol as [interval][4].
+struct gfhip_spectrum : flux_cells {
+    gfhip::flux::field field = {};
+    size_t ns = 0, nn = 0;
+    double sscale = 0.0, nscale = 0.0;
+    device_ptr<double> fpol;
 };
 
 #define GFHIP_TRY(ctx, call, what) do { if ((ctx)->check((call), (what))) return 1; } while (0)
@@ -1594,9 +1612,10 @@ static bool edges_increase(const double *edges, const size_t n) {
     return true;
 }
 
-//  Four fp64 buffers of at least `count` elements, or the message about `noun`; nothing is enqueued.
-static int fp64_columns(gfhip_context *ctx, const char *noun, const uint64_t (&keys)[4], const size_t count, double **columns) {
-    for (int c = 0; c < 4; c++) {
+//  N fp64 buffers of at least `count` elements, or the message about `noun`; nothing is enqueued.
+template<size_t N>
+static int fp64_columns(gfhip_context *ctx, const char *noun, const uint64_t (&keys)[N], const size_t count, double **columns) {
+    for (size_t c = 0; c < N; c++) {
         const buffer *found = find_buffer(ctx, keys[c]);
         if (!found) return 1;
         if (found->dtype != GFIR_F64) return ctx->fail(std::string(noun) + " takes fp64 buffers");
@@ -1735,6 +1754,42 @@ static const char *flux_map_of(const gfhip_flux_map *given, gfhip::flux::map &m)
     return nullptr;
 }
 
+//  The map checked and copied, its tables repacked to [table cell][16] (a lane's coefficients are one 128-byte line) and
+//  uploaded with the edges, the launch shape decided and the `count` cells allocated.  prepare: the deposit kernels'
+//  request for large dynamic LDS, made when the private path is taken.
+int flux_cells::create(gfhip_context *context, const gfhip_flux_map *given, const size_t count,
+                       const std::vector<double> &all_edges, hipError_t (*prepare)()) {
+    if (const char *refused = flux_map_of(given, map)) return context->fail(refused);
+    if (context->check(hipSetDevice(context->device), "hipSetDevice")) return 1;
+    gfhip::flux_launch_shape(count, all_edges.size(), !(given->flags & gfhip::flux::flag_no_private_sums), context->num_cus,
+                             &is_private, &cap, &block, &max_workgroups, &lds_bytes);
+    const size_t table = static_cast<size_t> (given->numr*given->numz);
+    std::vector<double> lines;
+    try {
+        lines.resize(table*16);
+    } catch (const std::bad_alloc &) {
+        return context->fail("a flux map's tables do not fit the host's memory");
+    }
+    for (size_t k = 0; k < 16; k++) {
+        const double *from = given->coefficients + k*table;
+        for (size_t at = 0; at < table; at++) lines[at*16 + k] = from[at];
+    }
+    return context->check(allocate(packed, lines.size()*sizeof(double)), "hipMalloc(flux tables)") ||
+           context->check(hipMemcpy(packed.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
+           context->check(allocate(edges, all_edges.size()*sizeof(double)), "hipMalloc(edges)") ||
+           context->check(hipMemcpy(edges.get(), all_edges.data(), all_edges.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
+           exact_cells::create(context, count) ||
+           (is_private && context->check(prepare(), "hipFuncSetAttribute(flux deposit)"));
+}
+
+void flux_cells::info_to(struct gfhip_flux_info *info) const {
+    info->private_sums = is_private ? 1u : 0u;
+    info->workgroup_size = block;
+    info->cap_cells = cap;
+    info->max_workgroups = max_workgroups;
+    info->lds_bytes = lds_bytes;
+}
+
 extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, size_t cells) {
     if (!ctx) return nullptr;
     if (!map || !edges) {
@@ -1750,35 +1805,8 @@ extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_ma
         return nullptr;
     }
     std::unique_ptr<gfhip_flux> f(new gfhip_flux);
-    if (const char *refused = flux_map_of(map, f->map)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    if (ctx->check(hipSetDevice(ctx->device), "hipSetDevice")) return nullptr;
     f->scale = static_cast<double> (cells)/(edges[cells] - edges[0]);
-    gfhip::flux_launch_shape(cells, !(map->flags & gfhip::flux::flag_no_private_sums), ctx->num_cus, &f->is_private, &f->cap,
-                             &f->block, &f->max_workgroups, &f->lds_bytes);
-//  [table cell][16]: a lane's coefficients are one 128-byte line.
-    const size_t table = static_cast<size_t> (map->numr*map->numz);
-    std::vector<double> packed;
-    try {
-        packed.resize(table*16);
-    } catch (const std::bad_alloc &) {
-        ctx->fail("a flux map's tables do not fit the host's memory");
-        return nullptr;
-    }
-    for (size_t k = 0; k < 16; k++) {
-        const double *from = map->coefficients + k*table;
-        for (size_t at = 0; at < table; at++) packed[at*16 + k] = from[at];
-    }
-    if (ctx->check(allocate(f->packed, packed.size()*sizeof(double)), "hipMalloc(flux tables)") ||
-        ctx->check(hipMemcpy(f->packed.get(), packed.data(), packed.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
-        ctx->check(allocate(f->edges, (cells + 1)*sizeof(double)), "hipMalloc(edges)") ||
-        ctx->check(hipMemcpy(f->edges.get(), edges, (cells + 1)*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
-        f->create(ctx, cells) ||
-        (f->is_private && ctx->check(gfhip::flux_prepare(), "hipFuncSetAttribute(flux deposit)"))) {
-        return nullptr;
-    }
+    if (f->create(ctx, map, cells, std::vector<double> (edges, edges + cells + 1), gfhip::flux_prepare)) return nullptr;
     ctx->fluxes.push_back(std::move(f));
     return ctx->fluxes.back().get();
 }
@@ -1836,11 +1864,7 @@ extern "C" int gfhip_flux_read(gfhip_flux *f, double divisor, double *values) {
 extern "C" int gfhip_flux_info(gfhip_flux *f, struct gfhip_flux_info *info) {
     if (!f) return 1;
     if (!info) return f->ctx->fail("gfhip_flux_info needs a destination");
-    info->private_sums = f->is_private ? 1u : 0u;
-    info->workgroup_size = f->block;
-    info->cap_cells = f->cap;
-    info->max_workgroups = f->max_workgroups;
-    info->lds_bytes = f->lds_bytes;
+    f->info_to(info);
     return 0;
 }
 
@@ -1866,6 +1890,182 @@ extern "C" int gfhip_flux_label_host(const gfhip_flux_map *map, const double *x,
         }
         for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
         label[s] = gfhip::flux::label_of(m, gfhip::flux::psi_of(c, tr, tz));
+    }
+    return 0;
+}
+
+//  Spectra over the flux label and N (flux_spectrum.hip, flux_label.hpp).  At most 4096 cells per axis and 2^16 in all
+//  (536 B each: 35 MB of state); the two axes' edges are staged in LDS on both paths.
+static const size_t spectrum_cell_limit = static_cast<size_t> (1) << 16;
+
+//  The scalars of a caller's field, or why it is refused.
+static const char *spectrum_field_of(const gfhip_spectrum_field *given, gfhip::flux::field &f) {
+    for (const double *table : given->fpol) {
+        if (!table) return "a spectrum's field needs its four fpol tables";
+    }
+    if (given->numpsi == 0 || given->numpsi > 0x7fffffffull) return "a spectrum's field needs 1 <= numpsi <= 2^31 - 1";
+    if (!std::isfinite(given->dpsi) || given->dpsi == 0.0 || !std::isfinite(given->c) || given->c == 0.0) {
+        return "dpsi and c of a spectrum's field must be finite and non-zero";
+    }
+    if (!std::isfinite(given->psimin)) return "psimin of a spectrum's field must be finite";
+    if (given->reserved != 0) return "the reserved field of a spectrum's field must be 0";
+    f.psimin = given->psimin;
+    f.dpsi = given->dpsi;
+    f.numpsi = static_cast<double> (given->numpsi);
+    f.last = static_cast<int> (given->numpsi - 1);
+    f.c = given->c;
+    return nullptr;
+}
+
+extern "C" gfhip_spectrum *gfhip_spectrum_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                                 const double *sedges, size_t ns, const double *nedges, size_t nn) {
+    if (!ctx) return nullptr;
+    if (!map || !field || !sedges || !nedges) {
+        ctx->fail("a spectrum needs a map, a field and two edge arrays");
+        return nullptr;
+    }
+    if (ns < 1 || ns > flux_cell_limit || nn < 1 || nn > flux_cell_limit) {
+        ctx->fail("a spectrum has 1 to 4096 cells per axis");
+        return nullptr;
+    }
+    if (ns*nn > spectrum_cell_limit) {
+        ctx->fail("a spectrum has at most 65536 cells (536 B each)");
+        return nullptr;
+    }
+    if (!edges_increase(sedges, ns) || !edges_increase(nedges, nn)) {
+        ctx->fail("the edges of a spectrum must be finite and strictly increasing");
+        return nullptr;
+    }
+    std::unique_ptr<gfhip_spectrum> s(new gfhip_spectrum);
+    if (const char *refused = spectrum_field_of(field, s->field)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    s->ns = ns;
+    s->nn = nn;
+    s->sscale = static_cast<double> (ns)/(sedges[ns] - sedges[0]);
+    s->nscale = static_cast<double> (nn)/(nedges[nn] - nedges[0]);
+    std::vector<double> edges(sedges, sedges + ns + 1);
+    edges.insert(edges.end(), nedges, nedges + nn + 1);
+//  [interval][4]: a lane's fpol coefficients are one 32-byte line.
+    std::vector<double> lines;
+    try {
+        lines.resize(static_cast<size_t> (field->numpsi)*4);
+    } catch (const std::bad_alloc &) {
+        ctx->fail("a spectrum's fpol tables do not fit the host's memory");
+        return nullptr;
+    }
+    for (size_t k = 0; k < 4; k++) {
+        for (size_t q = 0; q < field->numpsi; q++) lines[q*4 + k] = field->fpol[k][q];
+    }
+    if (s->create(ctx, map, ns*nn, edges, gfhip::spectrum_prepare) ||
+        ctx->check(allocate(s->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
+        ctx->check(hipMemcpy(s->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
+        return nullptr;
+    }
+    ctx->spectra.push_back(std::move(s));
+    return ctx->spectra.back().get();
+}
+
+extern "C" void gfhip_spectrum_destroy(gfhip_spectrum *s) {
+    destroy_in(&gfhip_context::spectra, s);
+}
+
+extern "C" int gfhip_spectrum_add(gfhip_spectrum *s, const uint64_t keys[8], size_t count) {
+    if (!s) return 1;
+    if (!keys) return s->ctx->fail("gfhip_spectrum_add needs its 8 keys");
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], keys[7]};
+    double *columns[8];
+    if (fp64_columns(s->ctx, "a spectrum", all, count, columns)) return 1;
+    return s->add(count, [&](const size_t first, const size_t piece) {
+        gfhip::launch_spectrum_deposit(columns, first, piece, s->map, s->field, s->packed.get(), s->fpol.get(), s->edges.get(),
+                                       s->ns, s->nn, s->sscale, s->nscale, s->is_private, s->block, s->max_workgroups,
+                                       s->lds_bytes, s->state.get(), s->counters.get(), s->ctx->stream);
+    });
+}
+
+extern "C" int gfhip_spectrum_npar(gfhip_spectrum *s, const uint64_t keys[7], uint64_t label_key, uint64_t npar_key, size_t count) {
+    if (!s) return 1;
+    gfhip_context *ctx = s->ctx;
+    if (!keys) return ctx->fail("gfhip_spectrum_npar needs its 7 keys");
+    const uint64_t all[9] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], label_key, npar_key};
+    double *columns[9];
+    if (fp64_columns(ctx, "a spectrum", all, count, columns)) return 1;
+    if (enter(ctx)) return 1;
+    gfhip::launch_spectrum_npar(columns, count, s->map, s->field, s->packed.get(), s->fpol.get(), columns[7], columns[8], ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "spectrum npar launch");
+    return 0;
+}
+
+extern "C" int gfhip_spectrum_counts(gfhip_spectrum *s, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
+    return s ? s->counts(samples, outside, skipped) : 1;
+}
+
+extern "C" int gfhip_spectrum_state(gfhip_spectrum *s, int64_t *limbs) {
+    if (!s) return 1;
+    if (!limbs) return s->ctx->fail("gfhip_spectrum_state needs a destination");
+    return s->state_to(limbs);
+}
+
+extern "C" int gfhip_spectrum_merge(gfhip_spectrum *s, const int64_t *limbs, size_t ns, size_t nn, uint64_t samples, uint64_t outside,
+                                    uint64_t skipped) {
+    if (!s) return 1;
+    if (!limbs) return s->ctx->fail("gfhip_spectrum_merge needs a state");
+    if (ns != s->ns || nn != s->nn) return s->ctx->fail("merge: a spectrum of another shape");
+    return s->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_spectrum_read(gfhip_spectrum *s, double divisor, double *values) {
+    if (!s) return 1;
+    if (!values) return s->ctx->fail("gfhip_spectrum_read needs a destination");
+    return s->read(divisor, values);
+}
+
+//  Not through enter(): as gfhip_flux_info.
+extern "C" int gfhip_spectrum_info(gfhip_spectrum *s, struct gfhip_flux_info *info) {
+    if (!s) return 1;
+    if (!info) return s->ctx->fail("gfhip_spectrum_info needs a destination");
+    s->info_to(info);
+    return 0;
+}
+
+//  Host side, no device: flux_label.hpp on the caller's 16 + 4 tables.
+extern "C" int gfhip_spectrum_npar_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *const columns[7],
+                                        size_t count, double *label, double *npar) {
+    if (!map || !field || !columns || ((!label || !npar) && count)) {
+        creation_error = "gfhip_spectrum_npar_host needs a map, a field, seven columns and two destinations";
+        return 1;
+    }
+    for (int k = 0; k < 7; k++) {
+        if (!columns[k] && count) {
+            creation_error = "gfhip_spectrum_npar_host needs a map, a field, seven columns and two destinations";
+            return 1;
+        }
+    }
+    gfhip::flux::map m;
+    gfhip::flux::field f;
+    const char *refused = flux_map_of(map, m);
+    if (!refused) refused = spectrum_field_of(field, f);
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    const size_t table = static_cast<size_t> (map->numr*map->numz);
+    for (size_t s = 0; s < count; s++) {
+        const double x = columns[0][s], y = columns[1][s];
+        double tr, tz, tp, gr, gz, c[16], cubic[4];
+        const long long at = gfhip::flux::locate(m, x, y, columns[2][s], tr, tz);
+        if (at < 0) {
+            label[s] = npar[s] = std::numeric_limits<double>::quiet_NaN();
+            continue;
+        }
+        for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
+        const double psi = gfhip::flux::psi_gradient(m, c, tr, tz, gr, gz);
+        label[s] = gfhip::flux::canonical(gfhip::flux::label_of(m, psi));
+        const int q = gfhip::flux::fpol_interval(f, psi, tp);
+        for (size_t k = 0; k < 4; k++) cubic[k] = field->fpol[k][q];
+        npar[s] = gfhip::flux::npar_of(f, x, y, gfhip::flux::radius_of(x, y), columns[3][s], columns[4][s], columns[5][s],
+                                       columns[6][s], gr, gz, gfhip::flux::fpol_of(cubic, tp));
     }
     return 0;
 }

@@ -1,5 +1,6 @@
-"""What a deposition grid (deposition.py) and a flux profile (flux.py) share: a store of exact sums on a context's
-device, cells x 67 limbs of csrc/superacc.hpp and three counters, behind gfhip_bins_* or gfhip_flux_* (include/gf_hip.h).
+"""What a deposition grid (deposition.py), a flux profile (flux.py) and a spectrum (spectrum.py) share: a store of exact
+sums on a context's device, cells x 67 limbs of csrc/superacc.hpp and three counters, behind gfhip_bins_*, gfhip_flux_*
+or gfhip_spectrum_* (include/gf_hip.h).
 They differ in how a sample finds its cell, which is the constructor's business."""
 import ctypes
 import os
@@ -58,12 +59,12 @@ class ExactCells:
         self.handle = None
 
 
-def bin_files(grid, directory, num_files, tag):
+def bin_files(grid, directory, num_files, tag, names=("x", "y", "z", "d_power")):
     """d_power of <directory>/result0.nc .. result<num_files - 1>.nc binned into `grid` (an ExactCells) through buffers
-    `<tag>_<name>_<rays>` of its context: (bins divided by the total number of rays, counts, that total)."""
+    `<tag>_<name>_<rays>` of its context: (bins divided by the total number of rays, counts, that total).  names: the
+    file's variables that grid.add takes, in its order."""
     from . import _lib
     context = grid.context
-    names = ("x", "y", "z", "d_power")
     total = 0
     for number in range(num_files):
         file = ResultFile(os.path.join(directory, "result%d.nc" % number))

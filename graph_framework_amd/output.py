@@ -434,6 +434,27 @@ def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside
     file.close()
 
 
+def write_spectrum_bins(path, bins, sbins, nbins, psi0, span, label="s", c=1.0, samples=0, outside=0, skipped=0):
+    """spectrum_bins.nc, flux_bins.nc with a second axis: dimensions ns, nsp, nn, nnp; f8 variables bins(ns, nn),
+    sbins(nsp), the edges in the label, and nbins(nnp), the edges in the parallel refractive index; what became of the
+    samples as global integer attributes; psi0, span and c (f8) and the label kind as global attributes."""
+    bins = np.asarray(bins)
+    if bins.ndim != 2:
+        raise ValueError("a spectrum's bins are (ns, nn)")
+    file = BinsFile(path)
+    for name, length in (("ns", bins.shape[0]), ("nsp", bins.shape[0] + 1), ("nn", bins.shape[1]), ("nnp", bins.shape[1] + 1)):
+        file.create_dimension(name, length)
+    file.write_variable("bins", bins, ("ns", "nn"))
+    file.write_variable("sbins", np.asarray(sbins).reshape(-1), ("nsp",))
+    file.write_variable("nbins", np.asarray(nbins).reshape(-1), ("nnp",))
+    _count_attributes(file, samples, outside, skipped)
+    file.float64_attribute("psi0", psi0)
+    file.float64_attribute("span", span)
+    file.text_attribute("label", label)
+    file.float64_attribute("c", c)
+    file.close()
+
+
 #  Variables of the reference's ray files, solver.hpp:338-346.
 RAY_VARIABLES = (("time", "t"), ("residual", "residual"), ("w", "w"), ("x", "x"), ("y", "y"), ("z", "z"),
                  ("kx", "kx"), ("ky", "ky"), ("kz", "kz"))

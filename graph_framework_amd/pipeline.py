@@ -13,7 +13,7 @@ initial values come from absorption.absorption_work / absorption.power_work, whi
 stores a record bit for bit, so what a later stage reads back from it is what the hand-over delivers; a real variable
 read into a complex data_set gets +0.0 imaginary parts (output.hpp:305, :425-428), which is the widening hand-over.
 """
-from .absorption import _Writer, absorption_work, power_work
+from .absorption import WAVE_NAMES, _Writer, absorption_work, allocate_wave_buffers, power_work
 from .backend import Context, key_of
 from .output import RAY_VARIABLES, ResultFile
 from . import _lib
@@ -29,7 +29,7 @@ class OnePass:
     source: the Context that holds the nine trajectory arrays of `num_rays` fp64 elements.
     keys: {file variable (output.RAY_VARIABLES): buffer key in `source`}; the solver's names by default.
     model: "weak_damping" or "root_find" (run_absorption's).  items: GFIR replacing exported workloads, {"weak_damping",
-    "init", "loss", "final", "power"}.  deposition, flux: as in absorption.bin_power.
+    "init", "loss", "final", "power"}.  deposition, flux, spectrum: as in absorption.bin_power.
     stream: the stream `source` launches on, when the caller knows it: the stage contexts then share it and nothing but
     stream order is needed between the stages; otherwise they get private streams and gfhip_hand_over orders them.
 
@@ -39,7 +39,7 @@ class OnePass:
     root_find synchronises per record in its converge loop, as RootFinder does."""
 
     def __init__(self, source, num_rays, path, model="weak_damping", index=0, stream=None, keys=None, deposition=None,
-                 items=None, flux=None):
+                 items=None, flux=None, spectrum=None):
         items = items or {}
         self.source = source
         self.num_rays = n = int(num_rays)
@@ -55,6 +55,10 @@ class OnePass:
         self.flux = flux
 #  (the caller's, its local twin on the power stage's context), as in absorption.bin_power
         self.grids = [(target, target.like(self.power.context)) for target in (deposition, flux) if target is not None]
+        self.spectrum = spectrum
+        self.spectra = [(spectrum, spectrum.like(self.power.context))] if spectrum is not None else []
+        if self.spectra:
+            allocate_wave_buffers(self.power.context, n)
 #  The record as the file takes it, on a stream of its own: the copies to the host overlap what `source` does next.
         self.gather = Context(index)
         self.file = ResultFile(path, n)
@@ -88,6 +92,9 @@ class OnePass:
             self.power.run()
         for _, local in self.grids:
             local.add("x", "y", "z", "d_power", self.num_rays)
+        for _, local in self.spectra:
+            power.hand_over(self.source, [(name, keys[name]) for name in WAVE_NAMES])
+            local.add("x", "y", "z", *WAVE_NAMES, "d_power", self.num_rays)
         gather = self.gather
         gather.hand_over(self.source, [(self._gathered(name), keys[name]) for name, _ in RAY_VARIABLES])
         gather.hand_over(absorption, [(self._gathered("kamp"), "kamp")])
@@ -100,12 +107,14 @@ class OnePass:
         self.sync.start(write)
 
     def close(self):
-        """Join the writer (its error surfaces here), merge the deposition grid and the flux profile and free the stage
-        contexts."""
+        """Join the writer (its error surfaces here), merge the deposition grid, the flux profile and the spectrum and
+        free the stage contexts."""
         try:
             self.sync.join()
         finally:
             self.file.close()
+            self.grids += self.spectra
+            self.spectra = []
             while self.grids:
                 target, local = self.grids.pop(0)
                 target.merge(local.state(), **local.counts())

@@ -422,6 +422,62 @@ int gfhip_flux_volumes_host(const struct gfhip_flux_map *map, const double *edge
                             const struct gfhip_flux_window *window, uint64_t first, uint64_t count,
                             int64_t *limbs, uint64_t counters[3]);
 
+/* Power spectrum over the flux label and the parallel refractive index: per-sample values binned on the label
+ * above AND on N = c (k.B)/(|B| w) at the sample's position, every cell the EXACT sum of its samples (state shape
+ * (ns, nn, 67), cell (is, in) at is*nn + in).
+ *
+ * The field direction (csrc/flux_label.hpp) is B = (psi_z/R, fpol/R, -psi_R/R) in (R, phi, z) with the common 1/R
+ * dropped.  fpol comes from the four tables fpol_c0 .. fpol_c3 (numpsi intervals of width dpsi from psimin), a cubic
+ * in the GLOBAL normalised tp, the interval clamped to the table.  R, tr, tz, the inside test, c[a][b], col_a, psi and
+ * the label are those of the flux profile; every line one IEEE fp64 operation in this order, nothing fused:
+ *     dcol_a = ((c[a][3]*3.0)*tz + c[a][2]*2.0)*tz + c[a][1]
+ *     psi_tz = ((dcol_3*tr + dcol_2)*tr + dcol_1)*tr + dcol_0;  psi_tr = ((col_3*3.0)*tr + col_2*2.0)*tr + col_1
+ *     gR = psi_tr/dr;  gZ = psi_tz/dz;  tp = (psi - psimin)/dpsi
+ *     q = 0 unless tp >= 0 (a NaN gives 0); numpsi - 1 if tp >= numpsi; else (int)tp
+ *     f = ((fpol_c3[q]*tp + fpol_c2[q])*tp + fpol_c1[q])*tp + fpol_c0[q]
+ *     a = kx*x + ky*y;  b = ky*x - kx*y
+ *     num = (a*gZ + b*f)/R - kz*gR;  den = sqrt((gZ*gZ + f*f) + gR*gR);  npar = (c*(num/den))/w
+ * A NaN label or npar is handed out as the quiet NaN without payload (0x7ff8000000000000).
+ * A sample belongs to cell (is, in) iff sedges[is] <= label < sedges[is+1] and nedges[in] <= npar < nedges[in+1].
+ * `outside`: off the map, off either axis, or a NaN or infinite label or npar (w = 0, R = 0, a zero field);
+ * `skipped`: inside with a NaN or infinite value.
+ *
+ * gfhip_spectrum_create: as gfhip_flux_create, with the field and two edge arrays.  Refused: what
+ *   gfhip_flux_create refuses for the map; either axis outside 1-4096 cells; ns*nn > 65536; edges not finite or
+ *   not strictly increasing; dpsi or c zero or not finite; psimin not finite; numpsi zero or above 2^31 - 1; a
+ *   missing fpol table; reserved != 0.  Up to 256 cells (ns*nn) every workgroup sums its deposits in LDS, unless
+ *   the map sets GFHIP_FLUX_NO_PRIVATE_SUMS; the state is the same bytes either way.
+ * gfhip_spectrum_add: keys = x, y, z, kx, ky, kz, w, value; fp64 buffers of at least `count` elements.
+ * gfhip_spectrum_npar: keys = x, y, z, kx, ky, kz, w; the label and npar of `count` points into two more fp64
+ *   buffers, both NaN outside the map, otherwise what the lines above give.
+ * gfhip_spectrum_counts / _state / _read / _info / _destroy: as the flux profile's; _merge takes both cell counts of
+ *   the incoming state and refuses another shape.
+ * gfhip_spectrum_npar_host: no device, no context; the same lines on the CPU from the caller's tables.  Errors:
+ *   gfhip_last_error(NULL). */
+typedef struct gfhip_spectrum gfhip_spectrum;
+
+struct gfhip_spectrum_field {
+    double psimin, dpsi;
+    uint64_t numpsi;
+    const double *fpol[4];       /* fpol_c0 .. fpol_c3, numpsi doubles each */
+    double c;                    /* the speed of light in the units of w/k */
+    uint64_t reserved;
+};
+
+gfhip_spectrum *gfhip_spectrum_create(gfhip_context *ctx, const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                                      const double *sedges, size_t ns, const double *nedges, size_t nn);
+int gfhip_spectrum_add(gfhip_spectrum *spectrum, const uint64_t keys[8], size_t count);
+int gfhip_spectrum_npar(gfhip_spectrum *spectrum, const uint64_t keys[7], uint64_t label_key, uint64_t npar_key, size_t count);
+int gfhip_spectrum_counts(gfhip_spectrum *spectrum, uint64_t *samples, uint64_t *outside, uint64_t *skipped);
+int gfhip_spectrum_state(gfhip_spectrum *spectrum, int64_t *limbs);
+int gfhip_spectrum_merge(gfhip_spectrum *spectrum, const int64_t *limbs, size_t ns, size_t nn, uint64_t samples, uint64_t outside,
+                         uint64_t skipped);
+int gfhip_spectrum_read(gfhip_spectrum *spectrum, double divisor, double *values);
+int gfhip_spectrum_info(gfhip_spectrum *spectrum, struct gfhip_flux_info *info);
+void gfhip_spectrum_destroy(gfhip_spectrum *spectrum);
+int gfhip_spectrum_npar_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                             const double *const columns[7], size_t count, double *label, double *npar);
+
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
  * Non-zero for a NaN or an infinity among the values (gfhip_last_error(NULL)). */
