@@ -10,6 +10,7 @@ with a record every `sub_steps`, result<rank>.nc) on the MI355X backend.
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --one-pass
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --flux-density 16 --flux-window 1.0,2.4,-1.0,1.0
     python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 16 --flux-tables tests/golden/efit_tables.npz --npar-bins 16 --npar-range -1,1 --one-pass
+    python examples/trace_rays.py --rays 10000 --dispersion ordinary_wave --steps 20000 --sub-steps 1000 --output /tmp/rays --absorption-model weak_damping --flux-bins 64 --flux-tables tests/golden/efit_tables.npz --flux-batches 16 --one-pass
     python examples/trace_rays.py --equilibrium vmec --rays 20000 --steps 10 --sub-steps 2 --output /tmp/vmec_rays
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/trace_rays.py ...
 
@@ -24,6 +25,9 @@ With --flux-bins and --flux-tables (alone or next to --bins) d_power is also bin
 the file also holds the cells' volumes and the power density, bins/volume.
 With --npar-bins N (and --npar-range) next to --flux-bins d_power is also binned over the flux label and the parallel
 refractive index N = c (k.B)/(|B| w) (graph_framework_amd/spectrum.py) and the rank writes <output>_spectrum<rank>.nc.
+With --flux-batches G the profile and the spectrum are also summed per batch of rays (graph_framework_amd/batches.py: ray r
+of the whole ensemble belongs to batch (r >> 6) % G) and their files get stderr, the standard error of bins from the
+spread of the batch means, with batch_bins and batch_rays.
 With --one-pass as well the same work items run on every record while the trace holds it in device memory
 (graph_framework_amd/pipeline.py): same file, same bits, written once, and no pass over the file afterwards.
 """
@@ -77,6 +81,9 @@ def main():
                              "the power density bins/volume, as volume and density in <output>_flux<rank>.nc")
     parser.add_argument("--flux-window", default=None, metavar="RLO,RHI,ZLO,ZHI",
                         help="with --flux-density: only the part of the map with RLO <= R < RHI and ZLO <= z < ZHI counts as volume")
+    parser.add_argument("--flux-batches", type=int, default=None, metavar="G",
+                        help="with --flux-bins: the sums of the flux profile (and of the spectrum) also per batch of rays, G "
+                             "batches of the whole ensemble (1 to 256), and their standard error as stderr next to bins")
     parser.add_argument("--npar-bins", type=int, default=None, metavar="N",
                         help="with --flux-bins and --flux-tables: absorbed power also over N uniform cells of the parallel "
                              "refractive index, as <output>_spectrum<rank>.nc")
@@ -101,6 +108,8 @@ def main():
         parser.error("--flux-density needs --flux-bins")
     if args.flux_window is not None and args.flux_density is None:
         parser.error("--flux-window needs --flux-density")
+    if args.flux_batches is not None and args.flux_bins is None:
+        parser.error("--flux-batches needs --flux-bins")
     if args.npar_bins is not None and args.flux_bins is None:
         parser.error("--npar-bins needs --flux-bins and --flux-tables")
     if args.npar_range != "-1,1" and args.npar_bins is None:
@@ -154,18 +163,33 @@ def main():
         low, high = (float(v) for v in args.flux_range.split(","))
         tables = dict(np.load(args.flux_tables))
         context = Context(local_rank)
-        return context, FluxProfile(context, tables, np.linspace(low, high, args.flux_bins + 1), sqrt_label=args.flux_sqrt)
+        return context, FluxProfile(context, tables, np.linspace(low, high, args.flux_bins + 1), sqrt_label=args.flux_sqrt,
+                                    batches=args.flux_batches)
+
+    def batch_statistics(cells, what):
+        """(bins, the writer's keywords) of a profile or spectrum with --flux-batches: this rank's rays are begin .. end
+        of the ensemble."""
+        from graph_framework_amd.batches import largest_relative_error
+        from graph_framework_amd.flux import marginal_bins
+        bins = marginal_bins(cells, end - begin)
+        extra = cells.error_variables(begin, end - begin)
+        print("rank %d: %s in %d batches of rays: largest relative standard error %.3e among the cells above 1 %% of the peak"
+              % (rank, what, args.flux_batches, largest_relative_error(bins, extra["stderr"])))
+        return bins, extra
 
     def write_flux(context, profile):
         from graph_framework_amd.output import write_flux_bins
         counts = profile.counts()
-        bins = profile.read(end - begin)
-        edges, psi0, span, kind = profile.edges, profile.psi0, profile.span, profile.label_kind
         extra = {}
+        if args.flux_batches is not None:
+            bins, extra = batch_statistics(profile, "flux profile")
+        else:
+            bins = profile.read(end - begin)
+        edges, psi0, span, kind = profile.edges, profile.psi0, profile.span, profile.label_kind
         if args.flux_density is not None:
             from graph_framework_amd.flux import density_variables
             window = [float(v) for v in args.flux_window.split(",")] if args.flux_window else None
-            extra = density_variables(profile, bins, args.flux_density, window)
+            extra.update(density_variables(profile, bins, args.flux_density, window))
         profile.close()
         context.close()
         write_flux_bins("%s_flux%d.nc" % (args.output, rank), bins, edges, psi0, span, kind, **counts, **extra)
@@ -182,15 +206,20 @@ def main():
         context = Context(local_rank)
 #  The tracer's w is omega/c (its dispersion relations read wpe2 + k.k - w*w), so N = k.B/(|B| w): c = 1.
         return context, FluxSpectrum(context, tables, np.linspace(low, high, args.flux_bins + 1),
-                                     np.linspace(npar_low, npar_high, args.npar_bins + 1), sqrt_label=args.flux_sqrt, c=1.0)
+                                     np.linspace(npar_low, npar_high, args.npar_bins + 1), sqrt_label=args.flux_sqrt, c=1.0,
+                                     batches=args.flux_batches)
 
     def write_spectrum(context, spectrum):
         from graph_framework_amd.output import write_spectrum_bins
         counts = spectrum.counts()
-        bins = spectrum.read(end - begin)
+        extra = {}
+        if args.flux_batches is not None:
+            bins, extra = batch_statistics(spectrum, "spectrum")
+        else:
+            bins = spectrum.read(end - begin)
         kind = spectrum.label_kind
         write_spectrum_bins("%s_spectrum%d.nc" % (args.output, rank), bins, spectrum.sedges, spectrum.nedges, spectrum.psi0,
-                            spectrum.span, kind, spectrum.c, **counts)
+                            spectrum.span, kind, spectrum.c, **counts, **extra)
         spectrum.close()
         context.close()
         print("rank %d: spectrum on %dx%d cells of %s and N: %d samples, %d outside, %d skipped; sum of bins %.6e"
@@ -207,7 +236,7 @@ def main():
         waves = flux_spectrum() if args.npar_bins else None
         writer = OnePass(solve.work.context, end - begin, path, model=args.absorption_model, index=local_rank,
                          stream=solve.torch_stream.cuda_stream, deposition=grid[1] if grid else None,
-                         flux=surfaces[1] if surfaces else None, spectrum=waves[1] if waves else None)
+                         flux=surfaces[1] if surfaces else None, spectrum=waves[1] if waves else None, first_ray=begin)
         write_step = writer.record
     else:
         writer = TrajectoryWriter(solve, path) if args.output else None
@@ -251,7 +280,7 @@ def main():
             surfaces = flux_profile() if args.flux_bins else None
             waves = flux_spectrum() if args.npar_bins else None
             bin_power(path, records, index=local_rank, deposition=grid[1] if grid else None,
-                      flux=surfaces[1] if surfaces else None, spectrum=waves[1] if waves else None)
+                      flux=surfaces[1] if surfaces else None, spectrum=waves[1] if waves else None, first_ray=begin)
             if grid:
                 write_deposition(*grid)
             if surfaces:

@@ -100,6 +100,12 @@ SYMBOLS = [
     ("gfhip_flux_label_host", _I, [_P, _P, _P, _P, _S, _P]),
     ("gfhip_flux_add_volumes", _I, [_P, _U32, _P, _U64, _U64]),
     ("gfhip_flux_volumes_host", _I, [_P, _P, _S, _U32, _P, _U64, _U64, _P, _P]),
+    ("gfhip_flux_create_batched", _P, [_P, _P, _P, _S, _S]),
+    ("gfhip_flux_add_rays", _I, [_P, _U64, _U64, _U64, _U64, _S, _U64]),
+    ("gfhip_flux_merge_batches", _I, [_P, _P, _S, _S, _U64, _U64, _U64]),
+    ("gfhip_spectrum_create_batched", _P, [_P, _P, _P, _P, _S, _P, _S, _S]),
+    ("gfhip_spectrum_add_rays", _I, [_P, _P, _S, _U64]),
+    ("gfhip_spectrum_merge_batches", _I, [_P, _P, _S, _S, _S, _U64, _U64, _U64]),
     ("gfhip_spectrum_create", _P, [_P, _P, _P, _P, _S, _P, _S]),
     ("gfhip_spectrum_add", _I, [_P, _P, _S]),
     ("gfhip_spectrum_npar", _I, [_P, _P, _U64, _U64, _S]),

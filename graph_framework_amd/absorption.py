@@ -156,7 +156,15 @@ def allocate_wave_buffers(context, num_rays):
         context._check(context.lib.gfhip_allocate_buffer(context.handle, key_of(name), num_rays, _lib.GFIR_F64))
 
 
-def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=None, flux=None, spectrum=None):
+def feed_cells(local, keys, count, first_ray):
+    """One record into a local twin: with its rays' indices if the twin keeps batches of rays (batches.py)."""
+    if getattr(local, "batches", None) is not None:
+        local.add_rays(*keys, count, first_ray)
+    else:
+        local.add(*keys, count)
+
+
+def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=None, flux=None, spectrum=None, first_ray=0):
     """bin_power's per-shard body (xrays.cpp:694-786).
 
     deposition: a deposition.Deposition (on any context).  Every record's x, y, z and d_power are then binned on
@@ -166,7 +174,8 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
     flux: a flux.FluxProfile (on any context), alone or next to `deposition`: the same records binned on its flux
     surfaces, the exact state merged into it at the end.
     spectrum: a spectrum.FluxSpectrum (on any context), alone or next to the others: the same records binned over the
-    flux label and N, with kx, ky, kz and w of every record uploaded from the file next to x, y, z."""
+    flux label and N, with kx, ky, kz and w of every record uploaded from the file next to x, y, z.
+    first_ray: the index of the file's first ray in the whole ensemble, for a `flux` or `spectrum` with batches."""
     file = ResultFile(filename)
     n = file.num_rays
     work, host, item = power_work(n, index, stream, item)
@@ -188,11 +197,11 @@ def bin_power(filename, num_steps, index=0, stream=None, item=None, deposition=N
     def feed(record):
         """The record's deposits, right behind d_power on the context's stream."""
         for _, local in grids:
-            local.add("x", "y", "z", "d_power", n)
+            feed_cells(local, ("x", "y", "z", "d_power"), n, first_ray)
         for _, local in spectra:
             for name in WAVE_NAMES:
                 work.context.copy_to_device(name, file.read(name, record))
-            local.add("x", "y", "z", *WAVE_NAMES, "d_power", n)
+            feed_cells(local, ("x", "y", "z") + WAVE_NAMES + ("d_power",), n, first_ray)
 
     if grids or spectra:
         for name in ("x", "y", "z"):

@@ -31,6 +31,13 @@ void launch_flux_deposit(const double *x, const double *y, const double *z, cons
                          const flux::map &m, const double *packed, const double *edges, const size_t cells, const double scale,
                          const bool is_private, const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
                          void *state, unsigned long long *counters, hipStream_t stream);
+//  The same with the samples' rays (ray_batches.hpp): sample i is ray first_ray + i; state: [batch][cell][limb]; the
+//  launch shape is that of `cells`, the cells of ONE batch.
+void launch_flux_deposit_rays(const double *x, const double *y, const double *z, const double *value, const size_t count,
+                              const unsigned long long first_ray, const size_t batch_count, const flux::map &m,
+                              const double *packed, const double *edges, const size_t cells, const double scale,
+                              const bool is_private, const unsigned int block, const size_t max_workgroups,
+                              const size_t lds_bytes, void *state, unsigned long long *counters, hipStream_t stream);
 //  The quadrature points first .. first + count of flux_label.hpp; row = numz*sub, twice_sub = (double)(2*sub).
 void launch_flux_volumes(const unsigned long long first, const size_t count, const unsigned long long row, const double twice_sub,
                          const double area, const flux::window &window, const flux::map &m, const double *packed,
@@ -48,6 +55,13 @@ void launch_spectrum_deposit(const double *const *columns, const size_t first, c
                              const size_t ns, const size_t nn, const double sscale, const double nscale, const bool is_private,
                              const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
                              void *state, unsigned long long *counters, hipStream_t stream);
+//  The same with the samples' rays: sample first + i of the columns is ray first_ray + i; state: [batch][is][in][limb].
+void launch_spectrum_deposit_rays(const double *const *columns, const size_t first, const size_t count,
+                                  const unsigned long long first_ray, const size_t batch_count, const flux::map &m,
+                                  const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                                  const size_t ns, const size_t nn, const double sscale, const double nscale,
+                                  const bool is_private, const unsigned int block, const size_t max_workgroups,
+                                  const size_t lds_bytes, void *state, unsigned long long *counters, hipStream_t stream);
 void launch_spectrum_npar(const double *const *columns, const size_t count, const flux::map &m, const flux::field &f,
                           const double *packed, const double *fpol, double *label, double *npar, hipStream_t stream);
 

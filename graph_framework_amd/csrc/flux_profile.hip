@@ -18,6 +18,9 @@
 ///  deposition.hip's deposit_kernel.  What a sample adds, the counters, the wave-level pre-sum and the atomic adds are
 ///  the functions of cell_deposit.hpp in both kernels; this one has the label and the private grid of its own.
 ///
+///  flux_deposit_rays_kernel keeps the same sums per batch of rays (ray_batches.hpp), state [batch][cell][limb]: a
+///  workgroup works on one batch at a time, so the private grid is still `cells` wide whatever the number of batches.
+///
 ///  flux_volume_kernel deposits the same way, but what it deposits it generates itself: the quadrature points of
 ///  flux_label.hpp, weight R x area each, so that a cell's sum is the volume/2 pi of the part of the map whose label
 ///  lies in the cell.  It reads no sample arrays.
@@ -73,6 +76,24 @@ flux_deposit_kernel(const double *__restrict__ x, const double *__restrict__ y, 
     }
     sums.close(state);
     deposit::flush(tally, counters);
+}
+
+//  flux_deposit_kernel with the samples' rays: sample i is ray first_ray + i, and the state is [batch][cell][limb]
+//  (flux_sums.hpp's deposit_batched).
+template<bool PRIVATE>
+__global__ void __launch_bounds__(private_block)
+flux_deposit_rays_kernel(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+                         const double *__restrict__ value, const unsigned long long count, const unsigned long long first_ray,
+                         const unsigned int batch_count, const flux::map m, const double *__restrict__ packed,
+                         const double *__restrict__ edges, const int cells, const double scale,
+                         unsigned long long *__restrict__ state, unsigned long long *__restrict__ counters) {
+    extern __shared__ unsigned long long shared[];
+    workgroup_sums<PRIVATE> sums;
+    sums.open(shared, edges, cells);
+    deposit_batched(sums, first_ray, count, batch_count, cells, state, counters, [&](const uint64_t at, double &v) {
+        v = value[at];
+        return deposit::find_cell(sums.staged, cells, scale, label_at(m, packed, x[at], y[at], z[at]));
+    });
 }
 
 //  The volume quadrature of flux_label.hpp: the points first .. first + count of the flat index t = gr*row + gz
@@ -154,6 +175,7 @@ void flux_launch_shape(const size_t cells, const size_t edge_count, const bool a
 //  profile: always the cap's size, so that no profile lowers what another one needs.
 hipError_t flux_prepare() {
     for (const void *kernel : {reinterpret_cast<const void *> (&flux_deposit_kernel<true>),
+                               reinterpret_cast<const void *> (&flux_deposit_rays_kernel<true>),
                                reinterpret_cast<const void *> (&flux_volume_kernel<true>)}) {
         const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                       static_cast<int> (private_cap_bytes));
@@ -177,6 +199,24 @@ void launch_flux_deposit(const double *x, const double *y, const double *z, cons
         hipLaunchKernelGGL(flux_deposit_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
                            static_cast<unsigned long long> (count), m, packed, edges, static_cast<int> (cells), scale,
                            static_cast<unsigned long long *> (state), counters);
+    }
+}
+
+void launch_flux_deposit_rays(const double *x, const double *y, const double *z, const double *value, const size_t count,
+                              const unsigned long long first_ray, const size_t batch_count, const flux::map &m,
+                              const double *packed, const double *edges, const size_t cells, const double scale,
+                              const bool is_private, const unsigned int block, const size_t max_workgroups,
+                              const size_t lds_bytes, void *state, unsigned long long *counters, hipStream_t stream) {
+    if (count == 0) return;
+    const unsigned int grid = batched_grid_of(count, block, max_workgroups, batch_count);
+    if (is_private) {
+        hipLaunchKernelGGL(flux_deposit_rays_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
+                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, packed,
+                           edges, static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
+    } else {
+        hipLaunchKernelGGL(flux_deposit_rays_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
+                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, packed,
+                           edges, static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
     }
 }
 

@@ -12,6 +12,9 @@
 ///  The sums are flux_sums.hpp's: up to 256 cells every workgroup owns the grid in LDS, the two axes' edges staged
 ///  behind it; above that, or with the map's no-private flag, deposits go to the global state behind the wave pre-sum.
 ///  The state does not depend on the route, the launch shape or the order of the samples.
+///
+///  spectrum_deposit_rays_kernel keeps the same sums per batch of rays (ray_batches.hpp), state [batch][is][in][limb],
+///  one batch at a time in a workgroup's LDS.
 //------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,6 +102,31 @@ spectrum_deposit_kernel(const spectrum_columns in, const unsigned long long coun
     deposit::flush(tally, counters);
 }
 
+//  spectrum_deposit_kernel with the samples' rays: sample i is ray first_ray + i, and the state is
+//  [batch][is][in][limb] (flux_sums.hpp's deposit_batched).
+template<bool PRIVATE>
+__global__ void __launch_bounds__(private_block)
+spectrum_deposit_rays_kernel(const spectrum_columns in, const unsigned long long count, const unsigned long long first_ray,
+                             const unsigned int batch_count, const flux::map m, const flux::field f,
+                             const double *__restrict__ packed, const double *__restrict__ fpol,
+                             const double *__restrict__ edges, const int ns, const int nn, const double sscale,
+                             const double nscale, unsigned long long *__restrict__ state,
+                             unsigned long long *__restrict__ counters) {
+    extern __shared__ unsigned long long shared[];
+    workgroup_sums<PRIVATE> sums;
+    sums.open(shared, edges, ns*nn, ns + nn + 2);
+    const double *sedge = sums.staged, *nedge = sums.staged + ns + 1;
+    deposit_batched(sums, first_ray, count, batch_count, ns*nn, state, counters, [&](const uint64_t at, double &v) {
+        v = in.value[at];
+        double label;
+        const double npar = npar_at(m, f, packed, fpol, in.x[at], in.y[at], in.z[at], in.kx[at], in.ky[at], in.kz[at],
+                                    in.w[at], label);
+        const int is = deposit::find_cell(sedge, ns, sscale, label);
+        const int in_n = deposit::find_cell(nedge, nn, nscale, npar);
+        return is >= 0 && in_n >= 0 ? is*nn + in_n : -1;
+    });
+}
+
 //  One lane per point: its label and its N, NaN outside the map.
 __global__ void __launch_bounds__(256)
 spectrum_npar_kernel(const spectrum_columns in, const unsigned long long count, const flux::map m, const flux::field f,
@@ -114,8 +142,13 @@ spectrum_npar_kernel(const spectrum_columns in, const unsigned long long count, 
 
 //  Dynamic LDS above 64 KiB has to be asked for: always the cap's size, as flux_prepare does.
 hipError_t spectrum_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *> (&spectrum_deposit_kernel<true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int> (private_cap_bytes));
+    for (const void *kernel : {reinterpret_cast<const void *> (&spectrum_deposit_kernel<true>),
+                               reinterpret_cast<const void *> (&spectrum_deposit_rays_kernel<true>)}) {
+        const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                      static_cast<int> (private_cap_bytes));
+        if (status != hipSuccess) return status;
+    }
+    return hipSuccess;
 }
 
 void launch_spectrum_deposit(const double *const *columns, const size_t first, const size_t count, const flux::map &m,
@@ -135,6 +168,29 @@ void launch_spectrum_deposit(const double *const *columns, const size_t first, c
         hipLaunchKernelGGL(spectrum_deposit_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, in,
                            static_cast<unsigned long long> (count), m, f, packed, fpol, edges, static_cast<int> (ns),
                            static_cast<int> (nn), sscale, nscale, static_cast<unsigned long long *> (state), counters);
+    }
+}
+
+void launch_spectrum_deposit_rays(const double *const *columns, const size_t first, const size_t count,
+                                  const unsigned long long first_ray, const size_t batch_count, const flux::map &m,
+                                  const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                                  const size_t ns, const size_t nn, const double sscale, const double nscale,
+                                  const bool is_private, const unsigned int block, const size_t max_workgroups,
+                                  const size_t lds_bytes, void *state, unsigned long long *counters, hipStream_t stream) {
+    if (count == 0) return;
+    const spectrum_columns in = {columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first,
+                                 columns[4] + first, columns[5] + first, columns[6] + first, columns[7] + first};
+    const unsigned int grid = batched_grid_of(count, block, max_workgroups, batch_count);
+    if (is_private) {
+        hipLaunchKernelGGL(spectrum_deposit_rays_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, f,
+                           packed, fpol, edges, static_cast<int> (ns), static_cast<int> (nn), sscale, nscale,
+                           static_cast<unsigned long long *> (state), counters);
+    } else {
+        hipLaunchKernelGGL(spectrum_deposit_rays_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, f,
+                           packed, fpol, edges, static_cast<int> (ns), static_cast<int> (nn), sscale, nscale,
+                           static_cast<unsigned long long *> (state), counters);
     }
 }
 

@@ -1,7 +1,8 @@
 //------------------------------------------------------------------------------
 ///  @file flux_sums.hpp
 ///  @brief What the deposit kernels of flux_profile.hip and flux_spectrum.hip share (device side): the label of a point
-///  from the repacked psi tables, and a workgroup's sums, private in LDS or global.
+///  from the repacked psi tables, a workgroup's sums, private in LDS or global, and the deposit of their batched
+///  variants, one batch of rays (ray_batches.hpp) at a time.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_FLUX_SUMS_HPP
 #define GFHIP_FLUX_SUMS_HPP
@@ -11,6 +12,7 @@
 
 #include "cell_deposit.hpp"
 #include "flux_label.hpp"
+#include "ray_batches.hpp"
 #include "superacc.hpp"
 
 namespace gfhip {
@@ -87,12 +89,64 @@ struct workgroup_sums {
             }
         }
     }
+
+//  Between two barriers: no wave adds to a limb that another one has yet to hand over.
+    __device__ __forceinline__ void drain(unsigned long long *__restrict__ state) const {
+        if constexpr (PRIVATE) {
+            __syncthreads();
+            for (unsigned int i = threadIdx.x; i < words; i += blockDim.x) {
+                const unsigned long long sum = shared[i];
+                if (sum) {
+                    atomicAdd(state + i, sum);
+                    shared[i] = 0ull;
+                }
+            }
+            __syncthreads();
+        }
+    }
 };
+
+//  The body of the batched deposit kernels.  The state is batch-major, [batch][cell][limb]: slab g is the state of the
+//  samples whose ray, first_ray + the sample's index, belongs to batch g.  The workgroup follows ray_batches.hpp's
+//  walk: it holds the sums of ONE batch at a time (`cells` of them, whatever the number of batches), its waves take
+//  that batch's chunks of 64 rays, and it drains into the batch's slab before it goes on.  On the global path the
+//  batch is part of the cell, g*cells + cell, and a wave still has one batch: the pre-sum keeps working.
+//  sample(at, value): the cell of sample `at`, or -1, and its value.  counters: samples, outside, skipped.
+template<bool PRIVATE, typename SAMPLE>
+__device__ __forceinline__ void deposit_batched(const workgroup_sums<PRIVATE> &sums, const unsigned long long first_ray,
+                                                const unsigned long long count, const unsigned int batch_count, const int cells,
+                                                unsigned long long *__restrict__ state,
+                                                unsigned long long *__restrict__ counters, SAMPLE sample) {
+    deposit::tallies tally;
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    batches::walk(first_ray, count, batch_count, gridDim.x, blockDim.x >> 6, blockIdx.x, wave,
+                  [&](const unsigned int g, const uint64_t chunk_ray) {
+                      uint64_t at;
+                      const bool present = batches::sample_of(first_ray, count, chunk_ray, lane, at);
+                      int cell = -1;                   // outside, as in the lanes that hold no sample
+                      double v = 0.0;
+                      if (present) cell = sample(at, v);
+                      const unsigned int slab = PRIVATE ? 0u : g*static_cast<unsigned int> (cells);
+                      const deposit::contribution a = deposit::contribution_of(cell >= 0, slab + static_cast<unsigned int> (cell), v);
+                      deposit::count(tally, present, a);
+                      sums.add(state, a);
+                  },
+                  [&](const unsigned int g) {
+                      sums.drain(state + static_cast<size_t> (g)*static_cast<size_t> (cells)*superacc::limbs);
+                  });
+    deposit::flush(tally, counters);
+}
 
 //  The workgroups of a launch of `count` samples.
 inline unsigned int grid_of(const size_t count, const unsigned int block, const size_t max_workgroups) {
     const size_t want = (count + block - 1)/block;
     return static_cast<unsigned int> (want < max_workgroups ? want : max_workgroups);
+}
+
+//  Those of a batched launch: with more than one per batch, a whole number per batch (ray_batches.hpp).
+inline unsigned int batched_grid_of(const size_t count, const unsigned int block, const size_t max_workgroups, const size_t batch_count) {
+    return batches::whole_teams(grid_of(count, block, max_workgroups), static_cast<unsigned int> (batch_count));
 }
 
 }  // namespace sums

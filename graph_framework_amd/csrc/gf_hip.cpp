@@ -37,6 +37,7 @@
 #include "converge_state.hpp"
 #include "flux_label.hpp"
 #include "hand_over.hpp"
+#include "ray_batches.hpp"
 #include "superacc.hpp"
 
 namespace gfhip {
@@ -235,10 +236,14 @@ struct flux_cells : exact_cells {
     bool is_private = false;
     size_t cap = 0, max_workgroups = 0, lds_bytes = 0;
     unsigned int block = 0;
+//  Batches of rays (ray_batches.hpp): 0 for a plain object; otherwise the state is [batch][cell][limb], `cells` counts
+//  all of them and `slab` those of one batch, which the launch shape is decided by.
+    size_t batches = 0, slab = 0;
 
     int create(gfhip_context *context, const gfhip_flux_map *given, size_t count, const std::vector<double> &all_edges,
-               hipError_t (*prepare)());
+               hipError_t (*prepare)(), size_t batch_count = 0);
     void info_to(struct gfhip_flux_info *info) const;
+    const char *rays_refused(uint64_t first_ray, size_t count) const;
 };
 
 //  A flux-surface profile.
@@ -1757,10 +1762,13 @@ static const char *flux_map_of(const gfhip_flux_map *given, gfhip::flux::map &m)
 //  The map checked and copied, its tables repacked to [table cell][16] (a lane's coefficients are one 128-byte line) and
 //  uploaded with the edges, the launch shape decided and the `count` cells allocated.  prepare: the deposit kernels'
 //  request for large dynamic LDS, made when the private path is taken.
+//  batch_count: 0, or the batches of rays a batched object keeps `count` cells each for.
 int flux_cells::create(gfhip_context *context, const gfhip_flux_map *given, const size_t count,
-                       const std::vector<double> &all_edges, hipError_t (*prepare)()) {
+                       const std::vector<double> &all_edges, hipError_t (*prepare)(), const size_t batch_count) {
     if (const char *refused = flux_map_of(given, map)) return context->fail(refused);
     if (context->check(hipSetDevice(context->device), "hipSetDevice")) return 1;
+    batches = batch_count;
+    slab = count;
     gfhip::flux_launch_shape(count, all_edges.size(), !(given->flags & gfhip::flux::flag_no_private_sums), context->num_cus,
                              &is_private, &cap, &block, &max_workgroups, &lds_bytes);
     const size_t table = static_cast<size_t> (given->numr*given->numz);
@@ -1778,8 +1786,22 @@ int flux_cells::create(gfhip_context *context, const gfhip_flux_map *given, cons
            context->check(hipMemcpy(packed.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
            context->check(allocate(edges, all_edges.size()*sizeof(double)), "hipMalloc(edges)") ||
            context->check(hipMemcpy(edges.get(), all_edges.data(), all_edges.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
-           exact_cells::create(context, count) ||
+           exact_cells::create(context, batch_count ? batch_count*count : count) ||
            (is_private && context->check(prepare(), "hipFuncSetAttribute(flux deposit)"));
+}
+
+//  The batches of a batched object, or why they are refused: 1 to 256, and at most 2^20 cells in all.
+static const char *batches_refused(const size_t batch_count, const size_t count) {
+    if (batch_count < 1 || batch_count > gfhip::batches::max_batches) return "a batched object has 1 to 256 batches";
+    if (batch_count*count > (static_cast<size_t> (1) << 20)) return "batches x cells is at most 2^20 (536 B each)";
+    return nullptr;
+}
+
+//  Why an add with a ray index is refused: only a batched object takes one, and first_ray + count fits 64 bits.
+const char *flux_cells::rays_refused(const uint64_t first_ray, const size_t count) const {
+    if (!batches) return "only a batched object (gfhip_flux_create_batched, gfhip_spectrum_create_batched) takes samples with a ray index";
+    if (first_ray + static_cast<uint64_t> (count) < first_ray) return "first_ray + count overflows 64 bits";
+    return nullptr;
 }
 
 void flux_cells::info_to(struct gfhip_flux_info *info) const {
@@ -1790,8 +1812,9 @@ void flux_cells::info_to(struct gfhip_flux_info *info) const {
     info->lds_bytes = lds_bytes;
 }
 
-extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, size_t cells) {
-    if (!ctx) return nullptr;
+//  batch_count: 0 for gfhip_flux_create.
+static gfhip_flux *flux_create(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, const size_t cells,
+                               const size_t batch_count) {
     if (!map || !edges) {
         ctx->fail("a flux profile needs a map and edges");
         return nullptr;
@@ -1806,9 +1829,23 @@ extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_ma
     }
     std::unique_ptr<gfhip_flux> f(new gfhip_flux);
     f->scale = static_cast<double> (cells)/(edges[cells] - edges[0]);
-    if (f->create(ctx, map, cells, std::vector<double> (edges, edges + cells + 1), gfhip::flux_prepare)) return nullptr;
+    if (f->create(ctx, map, cells, std::vector<double> (edges, edges + cells + 1), gfhip::flux_prepare, batch_count)) return nullptr;
     ctx->fluxes.push_back(std::move(f));
     return ctx->fluxes.back().get();
+}
+
+extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, size_t cells) {
+    return ctx ? flux_create(ctx, map, edges, cells, 0) : nullptr;
+}
+
+extern "C" gfhip_flux *gfhip_flux_create_batched(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, size_t cells,
+                                                 size_t batches) {
+    if (!ctx) return nullptr;
+    if (const char *refused = batches_refused(batches, cells)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    return flux_create(ctx, map, edges, cells, batches);
 }
 
 extern "C" void gfhip_flux_destroy(gfhip_flux *f) {
@@ -1817,12 +1854,27 @@ extern "C" void gfhip_flux_destroy(gfhip_flux *f) {
 
 extern "C" int gfhip_flux_add(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count) {
     if (!f) return 1;
+    if (f->batches) return f->ctx->fail("a batched flux profile takes its samples with their ray index: gfhip_flux_add_rays");
     double *columns[4];
     if (fp64_columns(f->ctx, "a flux profile", {x_key, y_key, z_key, value_key}, count, columns)) return 1;
     return f->add(count, [&](const size_t first, const size_t piece) {
         gfhip::launch_flux_deposit(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
                                    f->map, f->packed.get(), f->edges.get(), f->cells, f->scale, f->is_private, f->block,
                                    f->max_workgroups, f->lds_bytes, f->state.get(), f->counters.get(), f->ctx->stream);
+    });
+}
+
+extern "C" int gfhip_flux_add_rays(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count,
+                                   uint64_t first_ray) {
+    if (!f) return 1;
+    if (const char *refused = f->rays_refused(first_ray, count)) return f->ctx->fail(refused);
+    double *columns[4];
+    if (fp64_columns(f->ctx, "a flux profile", {x_key, y_key, z_key, value_key}, count, columns)) return 1;
+    return f->add(count, [&](const size_t first, const size_t piece) {
+        gfhip::launch_flux_deposit_rays(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
+                                        first_ray + first, f->batches, f->map, f->packed.get(), f->edges.get(), f->slab,
+                                        f->scale, f->is_private, f->block, f->max_workgroups, f->lds_bytes, f->state.get(),
+                                        f->counters.get(), f->ctx->stream);
     });
 }
 
@@ -1850,7 +1902,15 @@ extern "C" int gfhip_flux_state(gfhip_flux *f, int64_t *limbs) {
 extern "C" int gfhip_flux_merge(gfhip_flux *f, const int64_t *limbs, size_t cells, uint64_t samples, uint64_t outside, uint64_t skipped) {
     if (!f) return 1;
     if (!limbs) return f->ctx->fail("gfhip_flux_merge needs a state");
-    if (cells != f->cells) return f->ctx->fail("merge: a flux profile of another shape");
+    if (f->batches || cells != f->cells) return f->ctx->fail("merge: a flux profile of another shape");
+    return f->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_flux_merge_batches(gfhip_flux *f, const int64_t *limbs, size_t batches, size_t cells, uint64_t samples,
+                                        uint64_t outside, uint64_t skipped) {
+    if (!f) return 1;
+    if (!limbs) return f->ctx->fail("gfhip_flux_merge_batches needs a state");
+    if (!f->batches || batches != f->batches || cells != f->slab) return f->ctx->fail("merge: a flux profile of another shape");
     return f->merge(limbs, samples, outside, skipped);
 }
 
@@ -1917,9 +1977,10 @@ static const char *spectrum_field_of(const gfhip_spectrum_field *given, gfhip::f
     return nullptr;
 }
 
-extern "C" gfhip_spectrum *gfhip_spectrum_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                                 const double *sedges, size_t ns, const double *nedges, size_t nn) {
-    if (!ctx) return nullptr;
+//  batch_count: 0 for gfhip_spectrum_create.
+static gfhip_spectrum *spectrum_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                       const double *sedges, const size_t ns, const double *nedges, const size_t nn,
+                                       const size_t batch_count) {
     if (!map || !field || !sedges || !nedges) {
         ctx->fail("a spectrum needs a map, a field and two edge arrays");
         return nullptr;
@@ -1958,13 +2019,30 @@ extern "C" gfhip_spectrum *gfhip_spectrum_create(gfhip_context *ctx, const gfhip
     for (size_t k = 0; k < 4; k++) {
         for (size_t q = 0; q < field->numpsi; q++) lines[q*4 + k] = field->fpol[k][q];
     }
-    if (s->create(ctx, map, ns*nn, edges, gfhip::spectrum_prepare) ||
+    if (s->create(ctx, map, ns*nn, edges, gfhip::spectrum_prepare, batch_count) ||
         ctx->check(allocate(s->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
         ctx->check(hipMemcpy(s->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
         return nullptr;
     }
     ctx->spectra.push_back(std::move(s));
     return ctx->spectra.back().get();
+}
+
+extern "C" gfhip_spectrum *gfhip_spectrum_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                                 const double *sedges, size_t ns, const double *nedges, size_t nn) {
+    return ctx ? spectrum_create(ctx, map, field, sedges, ns, nedges, nn, 0) : nullptr;
+}
+
+extern "C" gfhip_spectrum *gfhip_spectrum_create_batched(gfhip_context *ctx, const gfhip_flux_map *map,
+                                                         const gfhip_spectrum_field *field, const double *sedges, size_t ns,
+                                                         const double *nedges, size_t nn, size_t batches) {
+    if (!ctx) return nullptr;
+//  Either axis has at most 4096 cells (checked below): the product cannot wrap here.
+    if (const char *refused = batches_refused(batches, ns <= flux_cell_limit && nn <= flux_cell_limit ? ns*nn : 0)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    return spectrum_create(ctx, map, field, sedges, ns, nedges, nn, batches);
 }
 
 extern "C" void gfhip_spectrum_destroy(gfhip_spectrum *s) {
@@ -1974,6 +2052,7 @@ extern "C" void gfhip_spectrum_destroy(gfhip_spectrum *s) {
 extern "C" int gfhip_spectrum_add(gfhip_spectrum *s, const uint64_t keys[8], size_t count) {
     if (!s) return 1;
     if (!keys) return s->ctx->fail("gfhip_spectrum_add needs its 8 keys");
+    if (s->batches) return s->ctx->fail("a batched spectrum takes its samples with their ray index: gfhip_spectrum_add_rays");
     const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], keys[7]};
     double *columns[8];
     if (fp64_columns(s->ctx, "a spectrum", all, count, columns)) return 1;
@@ -1981,6 +2060,21 @@ extern "C" int gfhip_spectrum_add(gfhip_spectrum *s, const uint64_t keys[8], siz
         gfhip::launch_spectrum_deposit(columns, first, piece, s->map, s->field, s->packed.get(), s->fpol.get(), s->edges.get(),
                                        s->ns, s->nn, s->sscale, s->nscale, s->is_private, s->block, s->max_workgroups,
                                        s->lds_bytes, s->state.get(), s->counters.get(), s->ctx->stream);
+    });
+}
+
+extern "C" int gfhip_spectrum_add_rays(gfhip_spectrum *s, const uint64_t keys[8], size_t count, uint64_t first_ray) {
+    if (!s) return 1;
+    if (!keys) return s->ctx->fail("gfhip_spectrum_add_rays needs its 8 keys");
+    if (const char *refused = s->rays_refused(first_ray, count)) return s->ctx->fail(refused);
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], keys[7]};
+    double *columns[8];
+    if (fp64_columns(s->ctx, "a spectrum", all, count, columns)) return 1;
+    return s->add(count, [&](const size_t first, const size_t piece) {
+        gfhip::launch_spectrum_deposit_rays(columns, first, piece, first_ray + first, s->batches, s->map, s->field,
+                                            s->packed.get(), s->fpol.get(), s->edges.get(), s->ns, s->nn, s->sscale, s->nscale,
+                                            s->is_private, s->block, s->max_workgroups, s->lds_bytes, s->state.get(),
+                                            s->counters.get(), s->ctx->stream);
     });
 }
 
@@ -2011,7 +2105,15 @@ extern "C" int gfhip_spectrum_merge(gfhip_spectrum *s, const int64_t *limbs, siz
                                     uint64_t skipped) {
     if (!s) return 1;
     if (!limbs) return s->ctx->fail("gfhip_spectrum_merge needs a state");
-    if (ns != s->ns || nn != s->nn) return s->ctx->fail("merge: a spectrum of another shape");
+    if (s->batches || ns != s->ns || nn != s->nn) return s->ctx->fail("merge: a spectrum of another shape");
+    return s->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_spectrum_merge_batches(gfhip_spectrum *s, const int64_t *limbs, size_t batches, size_t ns, size_t nn,
+                                            uint64_t samples, uint64_t outside, uint64_t skipped) {
+    if (!s) return 1;
+    if (!limbs) return s->ctx->fail("gfhip_spectrum_merge_batches needs a state");
+    if (!s->batches || batches != s->batches || ns != s->ns || nn != s->nn) return s->ctx->fail("merge: a spectrum of another shape");
     return s->merge(limbs, samples, outside, skipped);
 }
 
@@ -2095,6 +2197,7 @@ static const char *volume_points_of(const gfhip::flux::map &m, const uint32_t su
 
 extern "C" int gfhip_flux_add_volumes(gfhip_flux *f, uint32_t sub, const gfhip_flux_window *window, uint64_t first, uint64_t count) {
     if (!f) return 1;
+    if (f->batches) return f->ctx->fail("flux volumes have no rays: a batched flux profile does not take them");
     volume_points p;
     if (const char *refused = volume_points_of(f->map, sub, window, first, count, p)) return f->ctx->fail(refused);
     return f->add(count, [&](const size_t done, const size_t piece) {

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from .backend import GfHipError, key_of
-from .exact_cells import LIMBS, ExactCells, bin_files
+from .exact_cells import LIMBS, RayBatches, bin_files
 from .output import write_flux_bins
 
 SQRT_LABEL = 1
@@ -113,11 +113,13 @@ def volumes_host(tables, edges, sub, window=None, psi0=None, span=None, sqrt_lab
     return limbs, dict(zip(("samples", "outside", "skipped"), (int(c) for c in counters)))
 
 
-class FluxProfile(ExactCells):
-    """A radial profile of exact sums on a context's device (gfhip_flux_*, include/gf_hip.h); state() is (cells, 67)."""
+class FluxProfile(RayBatches):
+    """A radial profile of exact sums on a context's device (gfhip_flux_*, include/gf_hip.h); state() is (cells, 67).
+    batches=G: the same sums per batch of rays (batches.py), state() (G, cells, 67), fed with add_rays; total() is the
+    plain profile and standard_error() the error bar of its cells."""
     prefix = "flux"
 
-    def __init__(self, context, tables, edges, psi0=None, span=None, sqrt_label=False, private=True):
+    def __init__(self, context, tables, edges, psi0=None, span=None, sqrt_label=False, private=True, batches=None):
         self.tables = tables
         self.edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
         if self.edges.size < 2:
@@ -127,12 +129,16 @@ class FluxProfile(ExactCells):
         self.private = bool(private)
         given, keep = flux_map(tables, psi0, span, sqrt_label, private)
         self.psi0, self.span = given.psi0, given.span
-        self._created(context, (self.cells,), ctypes.byref(given), self.edges.ctypes.data, self.cells)
+        self._created_cells(context, batches, (self.cells,), ctypes.byref(given), self.edges.ctypes.data, self.cells)
         del keep                                             # the library has copied the tables
 
-    def like(self, context):
-        """An empty profile with this one's map, edges and options on another context."""
-        return FluxProfile(context, self.tables, self.edges, self.psi0, self.span, self.sqrt_label, self.private)
+    def _twin(self, context, batches):
+        return FluxProfile(context, self.tables, self.edges, self.psi0, self.span, self.sqrt_label, self.private, batches)
+
+    def add_rays(self, x_key, y_key, z_key, value_key, count, first_ray):
+        """add() for a profile with batches: sample i is ray first_ray + i of the whole ensemble."""
+        self.context._check(self.lib.gfhip_flux_add_rays(self.handle, key_of(x_key), key_of(y_key), key_of(z_key),
+                                                         key_of(value_key), int(count), int(first_ray)))
 
     @property
     def label_kind(self):
@@ -142,14 +148,6 @@ class FluxProfile(ExactCells):
         """The labels of `count` points into the fp64 buffer `label_key` (NaN outside the map); asynchronous."""
         self.context._check(self.lib.gfhip_flux_label(self.handle, key_of(x_key), key_of(y_key), key_of(z_key),
                                                       key_of(label_key), int(count)))
-
-    def merge(self, limbs, samples=0, outside=0, skipped=0):
-        """Add another profile's state() and counts() (same map and edges: the caller's business)."""
-        limbs = np.ascontiguousarray(limbs, dtype=np.int64)
-        if limbs.ndim != 2 or limbs.shape[1] != LIMBS:
-            raise ValueError("merge: limbs of shape %r are no (cells, %d) state" % (limbs.shape, LIMBS))
-        self.context._check(self.lib.gfhip_flux_merge(self.handle, limbs.ctypes.data, limbs.shape[0], int(samples), int(outside),
-                                                      int(skipped)))
 
     def add_volumes(self, sub=16, window=None, first=0, count=None):
         """Deposit the quadrature points first .. first + count (default: to the last) of include/gf_hip.h's flux
@@ -163,7 +161,7 @@ class FluxProfile(ExactCells):
     def volumes(self, sub=16, window=None, first=0, count=None):
         """(volume[cells] in m^3, counts): 2 pi times the exact sum of R dR dz over the part of the map (or window)
         whose label lies in each cell, on a twin of this profile.  Between closed surfaces that is the shell's volume."""
-        twin = self.like(self.context)
+        twin = self._twin(self.context, None)
         try:
             twin.add_volumes(sub, window, first, count)
             return twin.read()*(2.0*np.pi), twin.counts()
@@ -184,24 +182,39 @@ class FluxProfile(ExactCells):
 
 
 def flux_deposition(directory, num_files, tables, cells, low, high, psi0=None, span=None, sqrt_label=False, private=True,
-                    index=0, profile=None, density=False, sub=16, window=None):
+                    index=0, profile=None, density=False, sub=16, window=None, batches=None, first_ray=0):
     """bin_deposition's counterpart on flux surfaces: d_power of result0.nc .. result<num_files - 1>.nc binned on
     `cells` uniform cells of the label between `low` and `high`, divided by the total number of rays, written to
     <directory>/flux_bins.nc.  Returns (bins, counts).  profile: a FluxProfile that receives the exact state as well.
-    density: the file also gets the cells' volumes (FluxProfile.volumes(sub, window)) and bins/volume."""
+    density: the file also gets the cells' volumes (FluxProfile.volumes(sub, window)) and bins/volume.
+    batches: the sums are kept per batch of rays (`profile`, if given, has the same batches), the rays counted on from
+    first_ray across the files, and the file also gets stderr, batch_bins and batch_rays (write_flux_bins)."""
     from .backend import Context
     edges = np.linspace(low, high, cells + 1)
     context = Context(index)
-    local = FluxProfile(context, tables, edges, psi0, span, sqrt_label, private)
-    bins, counts, _ = bin_files(local, directory, num_files, "flux")
+    local = FluxProfile(context, tables, edges, psi0, span, sqrt_label, private, batches)
+    bins, counts, total = bin_files(local, directory, num_files, "flux", first_ray=first_ray)
     if profile is not None:
         profile.merge(local.state(), **counts)
     psi0, span, kind = local.psi0, local.span, local.label_kind
-    extra = density_variables(local, bins, sub, window) if density else {}
+    extra = {}
+    if batches is not None:
+        bins, extra = marginal_bins(local, total), local.error_variables(first_ray, total)
+    if density:
+        extra.update(density_variables(local, bins, sub, window))
     local.close()
     context.close()
     write_flux_bins(os.path.join(directory, "flux_bins.nc"), bins, edges, psi0, span, kind, **counts, **extra)
     return bins, counts
+
+
+def marginal_bins(batched, divisor=1.0):
+    """total().read(divisor) of a profile or a spectrum with batches: the bins of the plain object."""
+    marginal = batched.total()
+    try:
+        return marginal.read(divisor)
+    finally:
+        marginal.close()
 
 
 def density_variables(profile, bins, sub, window=None):

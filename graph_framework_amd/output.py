@@ -405,13 +405,33 @@ def write_bins(path, bins, xbins, ybins, zbins, samples=0, outside=0, skipped=0)
     file.close()
 
 
+def _batch_variables(file, cell_dimensions, cell_shape, stderr, batch_bins, batch_rays):
+    """The batch statistics of a tally (batches.py), each optional: stderr on the cells' dimensions; batch_bins, the
+    batch means, on (nb,) + those; batch_rays(nb), the rays of every batch (f8, as every variable).  Written last: a
+    file without them is the file it was."""
+    given = [np.asarray(v) for v in (batch_bins, batch_rays) if v is not None]
+    if given:
+        if len({v.shape[0] for v in given}) != 1:
+            raise ValueError("batch_bins and batch_rays differ in their number of batches")
+        file.create_dimension("nb", given[0].shape[0])
+    if stderr is not None:
+        file.write_variable("stderr", np.asarray(stderr).reshape(cell_shape), cell_dimensions)
+    if batch_bins is not None:
+        batch_bins = np.asarray(batch_bins)
+        file.write_variable("batch_bins", batch_bins.reshape((batch_bins.shape[0],) + tuple(cell_shape)), ("nb",) + cell_dimensions)
+    if batch_rays is not None:
+        file.write_variable("batch_rays", np.asarray(batch_rays, dtype=np.float64).reshape(-1), ("nb",))
+
+
 def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside=0, skipped=0, volume=None, density=None,
-                    sub=None, window=None):
+                    sub=None, window=None, stderr=None, batch_bins=None, batch_rays=None):
     """flux_bins.nc, the radial counterpart of bins.nc: dimensions ns, nsp; f8 variables bins(ns), sbins(nsp), the edges
     in the label; what became of the samples as global integer attributes; psi0 and span (f8) and the label kind ("s":
     (psi - psi0)/span, "sqrt_s": its square root) as global attributes.  With `volume` and `density` (both or neither)
     also the f8 variables volume(ns), the cells' volumes in m^3, and density(ns), and the quadrature they came from as
-    global attributes: sub (integer) and window (four f8: rlo, rhi, zlo, zhi; infinite where there was no window)."""
+    global attributes: sub (integer) and window (four f8: rlo, rhi, zlo, zhi; infinite where there was no window).
+    With stderr, batch_bins, batch_rays (each optional; a profile with batches' error_variables) also the f8 variables
+    stderr(ns), the standard error of bins, batch_bins(nb, ns), the batch means, and batch_rays(nb) on a dimension nb."""
     if (volume is None) != (density is None):
         raise ValueError("volume and density go together")
     if volume is not None and sub is None:
@@ -431,13 +451,16 @@ def write_flux_bins(path, bins, sbins, psi0, span, label="s", samples=0, outside
         file.write_variable("density", np.asarray(density).reshape(-1), ("ns",))
         file.int64_attribute("sub", sub)
         file.float64_attribute("window", (-np.inf, np.inf, -np.inf, np.inf) if window is None else window)
+    _batch_variables(file, ("ns",), (bins.size,), stderr, batch_bins, batch_rays)
     file.close()
 
 
-def write_spectrum_bins(path, bins, sbins, nbins, psi0, span, label="s", c=1.0, samples=0, outside=0, skipped=0):
+def write_spectrum_bins(path, bins, sbins, nbins, psi0, span, label="s", c=1.0, samples=0, outside=0, skipped=0, stderr=None,
+                        batch_bins=None, batch_rays=None):
     """spectrum_bins.nc, flux_bins.nc with a second axis: dimensions ns, nsp, nn, nnp; f8 variables bins(ns, nn),
     sbins(nsp), the edges in the label, and nbins(nnp), the edges in the parallel refractive index; what became of the
-    samples as global integer attributes; psi0, span and c (f8) and the label kind as global attributes."""
+    samples as global integer attributes; psi0, span and c (f8) and the label kind as global attributes.  With stderr,
+    batch_bins, batch_rays (each optional) also stderr(ns, nn), batch_bins(nb, ns, nn) and batch_rays(nb)."""
     bins = np.asarray(bins)
     if bins.ndim != 2:
         raise ValueError("a spectrum's bins are (ns, nn)")
@@ -452,6 +475,7 @@ def write_spectrum_bins(path, bins, sbins, nbins, psi0, span, label="s", c=1.0, 
     file.float64_attribute("span", span)
     file.text_attribute("label", label)
     file.float64_attribute("c", c)
+    _batch_variables(file, ("ns", "nn"), bins.shape, stderr, batch_bins, batch_rays)
     file.close()
 
 

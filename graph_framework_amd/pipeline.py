@@ -13,7 +13,7 @@ initial values come from absorption.absorption_work / absorption.power_work, whi
 stores a record bit for bit, so what a later stage reads back from it is what the hand-over delivers; a real variable
 read into a complex data_set gets +0.0 imaginary parts (output.hpp:305, :425-428), which is the widening hand-over.
 """
-from .absorption import WAVE_NAMES, _Writer, absorption_work, allocate_wave_buffers, power_work
+from .absorption import WAVE_NAMES, _Writer, absorption_work, allocate_wave_buffers, feed_cells, power_work
 from .backend import Context, key_of
 from .output import RAY_VARIABLES, ResultFile
 from . import _lib
@@ -29,7 +29,7 @@ class OnePass:
     source: the Context that holds the nine trajectory arrays of `num_rays` fp64 elements.
     keys: {file variable (output.RAY_VARIABLES): buffer key in `source`}; the solver's names by default.
     model: "weak_damping" or "root_find" (run_absorption's).  items: GFIR replacing exported workloads, {"weak_damping",
-    "init", "loss", "final", "power"}.  deposition, flux, spectrum: as in absorption.bin_power.
+    "init", "loss", "final", "power"}.  deposition, flux, spectrum, first_ray: as in absorption.bin_power.
     stream: the stream `source` launches on, when the caller knows it: the stage contexts then share it and nothing but
     stream order is needed between the stages; otherwise they get private streams and gfhip_hand_over orders them.
 
@@ -39,10 +39,11 @@ class OnePass:
     root_find synchronises per record in its converge loop, as RootFinder does."""
 
     def __init__(self, source, num_rays, path, model="weak_damping", index=0, stream=None, keys=None, deposition=None,
-                 items=None, flux=None, spectrum=None):
+                 items=None, flux=None, spectrum=None, first_ray=0):
         items = items or {}
         self.source = source
         self.num_rays = n = int(num_rays)
+        self.first_ray = int(first_ray)
         self.keys = dict(RAY_VARIABLES)
         self.keys.update(keys or {})
         self.absorption, _, self.newton = absorption_work(n, model, index, stream, items)
@@ -91,10 +92,10 @@ class OnePass:
             power.hand_over(absorption, [("kamp", "kamp", 1)])              # reference_imag_variable
             self.power.run()
         for _, local in self.grids:
-            local.add("x", "y", "z", "d_power", self.num_rays)
+            feed_cells(local, ("x", "y", "z", "d_power"), self.num_rays, self.first_ray)
         for _, local in self.spectra:
             power.hand_over(self.source, [(name, keys[name]) for name in WAVE_NAMES])
-            local.add("x", "y", "z", *WAVE_NAMES, "d_power", self.num_rays)
+            feed_cells(local, ("x", "y", "z") + WAVE_NAMES + ("d_power",), self.num_rays, self.first_ray)
         gather = self.gather
         gather.hand_over(self.source, [(self._gathered(name), keys[name]) for name, _ in RAY_VARIABLES])
         gather.hand_over(absorption, [(self._gathered("kamp"), "kamp")])

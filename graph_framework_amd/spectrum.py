@@ -13,8 +13,8 @@ import os
 import numpy as np
 
 from .backend import GfHipError, key_of
-from .exact_cells import LIMBS, ExactCells, bin_files
-from .flux import FluxProfile, _Info, flux_map
+from .exact_cells import RayBatches, bin_files
+from .flux import FluxProfile, _Info, flux_map, marginal_bins
 from .output import write_spectrum_bins
 
 #  dispersion.hpp:494-502: the speed of light the dispersion relations use, 1/sqrt(epsilon0 mu0)
@@ -63,12 +63,13 @@ def npar_host(tables, x, y, z, kx, ky, kz, w, psi0=None, span=None, sqrt_label=F
     return label, npar
 
 
-class FluxSpectrum(ExactCells):
+class FluxSpectrum(RayBatches):
     """A grid of exact sums over (label, N) on a context's device (gfhip_spectrum_*, include/gf_hip.h); state() is
-    (ns, nn, 67)."""
+    (ns, nn, 67).  batches=G: the same sums per batch of rays (batches.py), state() (G, ns, nn, 67), fed with add_rays."""
     prefix = "spectrum"
 
-    def __init__(self, context, tables, sedges, nedges, psi0=None, span=None, sqrt_label=False, private=True, c=None):
+    def __init__(self, context, tables, sedges, nedges, psi0=None, span=None, sqrt_label=False, private=True, c=None,
+                 batches=None):
         self.tables = tables
         self.sedges = np.ascontiguousarray(sedges, dtype=np.float64).reshape(-1)
         self.nedges = np.ascontiguousarray(nedges, dtype=np.float64).reshape(-1)
@@ -79,14 +80,19 @@ class FluxSpectrum(ExactCells):
         given, keep = flux_map(tables, psi0, span, sqrt_label, private)
         field, keep_field = spectrum_field(tables, c)
         self.psi0, self.span, self.c = given.psi0, given.span, field.c
-        self._created(context, (self.sedges.size - 1, self.nedges.size - 1), ctypes.byref(given), ctypes.byref(field),
-                      self.sedges.ctypes.data, self.sedges.size - 1, self.nedges.ctypes.data, self.nedges.size - 1)
+        self._created_cells(context, batches, (self.sedges.size - 1, self.nedges.size - 1), ctypes.byref(given),
+                            ctypes.byref(field), self.sedges.ctypes.data, self.sedges.size - 1, self.nedges.ctypes.data,
+                            self.nedges.size - 1)
         del keep, keep_field                                 # the library has copied the tables
 
-    def like(self, context):
-        """An empty spectrum with this one's map, field, edges and options on another context."""
+    def _twin(self, context, batches):
         return FluxSpectrum(context, self.tables, self.sedges, self.nedges, self.psi0, self.span, self.sqrt_label, self.private,
-                            self.c)
+                            self.c, batches)
+
+    def add_rays(self, x_key, y_key, z_key, kx_key, ky_key, kz_key, w_key, value_key, count, first_ray):
+        """add() for a spectrum with batches: sample i is ray first_ray + i of the whole ensemble."""
+        keys = _keys((x_key, y_key, z_key, kx_key, ky_key, kz_key, w_key, value_key), 8)
+        self.context._check(self.lib.gfhip_spectrum_add_rays(self.handle, keys, int(count), int(first_ray)))
 
     @property
     def label_kind(self):
@@ -103,24 +109,16 @@ class FluxSpectrum(ExactCells):
         keys = _keys((x_key, y_key, z_key, kx_key, ky_key, kz_key, w_key), 7)
         self.context._check(self.lib.gfhip_spectrum_npar(self.handle, keys, key_of(label_key), key_of(npar_key), int(count)))
 
-    def merge(self, limbs, samples=0, outside=0, skipped=0):
-        """Add another spectrum's state() and counts() (same map, field and edges: the caller's business)."""
-        limbs = np.ascontiguousarray(limbs, dtype=np.int64)
-        if limbs.ndim != 3 or limbs.shape[2] != LIMBS:
-            raise ValueError("merge: limbs of shape %r are no (ns, nn, %d) state" % (limbs.shape, LIMBS))
-        self.context._check(self.lib.gfhip_spectrum_merge(self.handle, limbs.ctypes.data, limbs.shape[0], limbs.shape[1],
-                                                          int(samples), int(outside), int(skipped)))
-
     def profile(self, context=None):
         """A FluxProfile on the label edges (on `context`, this spectrum's by default) that holds the marginal over N:
-        the nn slices state()[:, n, :] merged into it, which is exact.  Its counts are this spectrum's: a sample that
-        fell off the N axis is among `outside`."""
+        the nn slices state()[..., n, :] merged into it, which is exact.  Its counts are this spectrum's: a sample that
+        fell off the N axis is among `outside`.  A spectrum with batches gives a profile with the same batches."""
         marginal = FluxProfile(context or self.context, self.tables, self.sedges, self.psi0, self.span, self.sqrt_label,
-                               self.private)
+                               self.private, self.batches)
         state = self.state()
         counts = self.counts()
-        for n in range(self.shape[1]):
-            marginal.merge(state[:, n, :], **(counts if n == 0 else {}))
+        for n in range(self.cell_shape[1]):
+            marginal.merge(state[..., n, :], **(counts if n == 0 else {}))
         return marginal
 
     def info(self):
@@ -133,21 +131,25 @@ class FluxSpectrum(ExactCells):
 
 
 def spectrum_deposition(directory, num_files, tables, cells, low, high, npar_cells, npar_low, npar_high, psi0=None, span=None,
-                        sqrt_label=False, private=True, c=None, index=0, spectrum=None):
+                        sqrt_label=False, private=True, c=None, index=0, spectrum=None, batches=None, first_ray=0):
     """flux_deposition's counterpart over (label, N): d_power of result0.nc .. result<num_files - 1>.nc binned on
     `cells` uniform cells of the label between `low` and `high` times `npar_cells` of N between `npar_low` and
     `npar_high`, from x, y, z, kx, ky, kz, w of every record, divided by the total number of rays, written to
-    <directory>/spectrum_bins.nc.  Returns (bins, counts).  spectrum: a FluxSpectrum that receives the exact state too."""
+    <directory>/spectrum_bins.nc.  Returns (bins, counts).  spectrum: a FluxSpectrum that receives the exact state too.
+    batches, first_ray: as in flux_deposition."""
     from .backend import Context
     sedges = np.linspace(low, high, cells + 1)
     nedges = np.linspace(npar_low, npar_high, npar_cells + 1)
     context = Context(index)
-    local = FluxSpectrum(context, tables, sedges, nedges, psi0, span, sqrt_label, private, c)
-    bins, counts, _ = bin_files(local, directory, num_files, "spectrum", SAMPLE_NAMES + ("d_power",))
+    local = FluxSpectrum(context, tables, sedges, nedges, psi0, span, sqrt_label, private, c, batches)
+    bins, counts, total = bin_files(local, directory, num_files, "spectrum", SAMPLE_NAMES + ("d_power",), first_ray)
     if spectrum is not None:
         spectrum.merge(local.state(), **counts)
     psi0, span, kind, c = local.psi0, local.span, local.label_kind, local.c
+    extra = {}
+    if batches is not None:
+        bins, extra = marginal_bins(local, total), local.error_variables(first_ray, total)
     local.close()
     context.close()
-    write_spectrum_bins(os.path.join(directory, "spectrum_bins.nc"), bins, sedges, nedges, psi0, span, kind, c, **counts)
+    write_spectrum_bins(os.path.join(directory, "spectrum_bins.nc"), bins, sedges, nedges, psi0, span, kind, c, **counts, **extra)
     return bins, counts

@@ -379,7 +379,26 @@ void gfhip_bins_destroy(gfhip_bins *bins);
  *   Refused before any launch: sub outside 1-256; first + count beyond the total (or overflowing); a window
  *   with a NaN or lo >= hi (+-inf is allowed); a map with dr <= 0, dz <= 0 or rmin < 0.
  * gfhip_flux_volumes_host: no device, no context; the same points on the CPU with the same refusals, added to
- *   the cells*67 `limbs` (which are then canonical) and to the three counters.  Errors: gfhip_last_error(NULL). */
+ *   the cells*67 `limbs` (which are then canonical) and to the three counters.  Errors: gfhip_last_error(NULL).
+ *
+ * Batches of rays: a cell of a profile is a Monte-Carlo estimate, the mean over rays of what each ray left in it, and
+ * the spread of the same tally kept per batch of rays gives its standard error.  The batch rule
+ * (csrc/ray_batches.hpp): ray r is the ray's index in the whole ensemble over all ranks and files; 64 consecutive
+ * rays are a chunk, r >> 6, and with G batches ray r belongs to batch (r >> 6) % G.  A batched profile has the state
+ * (G, cells, 67), batch-major: slab g is the state an ordinary profile has after the samples of batch g's rays, so
+ * the sum of the slabs is the ordinary profile to the last bit, and batched states of shards merge exactly.
+ *
+ * gfhip_flux_create_batched: gfhip_flux_create with 1 <= batches <= 256 and batches*cells <= 2^20 (536 B each).
+ *   A workgroup sums one batch at a time, so the LDS path is taken up to 256 cells PER BATCH; gfhip_flux_info
+ *   describes that launch.
+ * gfhip_flux_add_rays: gfhip_flux_add for a batched profile: sample i is ray first_ray + i.  Refused: a profile
+ *   without batches; first_ray + count overflowing 64 bits.  gfhip_flux_add (no ray index) and
+ *   gfhip_flux_add_volumes (no rays) refuse a batched profile.
+ * gfhip_flux_counts / _state / _read / _info / _destroy serve a batched profile, _state and _read in the batch-major
+ *   shape (batches*cells*67 limbs, batches*cells values).  The counters are those of all samples.
+ * gfhip_flux_merge_batches: gfhip_flux_merge for a batched profile; it takes the number of batches and of cells per
+ *   batch of the incoming state and refuses another shape, as it refuses a profile without batches;
+ *   gfhip_flux_merge refuses a batched profile. */
 typedef struct gfhip_flux gfhip_flux;
 
 #define GFHIP_FLUX_SQRT_LABEL 1u
@@ -422,6 +441,13 @@ int gfhip_flux_volumes_host(const struct gfhip_flux_map *map, const double *edge
                             const struct gfhip_flux_window *window, uint64_t first, uint64_t count,
                             int64_t *limbs, uint64_t counters[3]);
 
+gfhip_flux *gfhip_flux_create_batched(gfhip_context *ctx, const struct gfhip_flux_map *map, const double *edges, size_t cells,
+                                      size_t batches);
+int gfhip_flux_add_rays(gfhip_flux *flux, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count,
+                        uint64_t first_ray);
+int gfhip_flux_merge_batches(gfhip_flux *flux, const int64_t *limbs, size_t batches, size_t cells, uint64_t samples,
+                             uint64_t outside, uint64_t skipped);
+
 /* Power spectrum over the flux label and the parallel refractive index: per-sample values binned on the label
  * above AND on N = c (k.B)/(|B| w) at the sample's position, every cell the EXACT sum of its samples (state shape
  * (ns, nn, 67), cell (is, in) at is*nn + in).
@@ -453,7 +479,10 @@ int gfhip_flux_volumes_host(const struct gfhip_flux_map *map, const double *edge
  * gfhip_spectrum_counts / _state / _read / _info / _destroy: as the flux profile's; _merge takes both cell counts of
  *   the incoming state and refuses another shape.
  * gfhip_spectrum_npar_host: no device, no context; the same lines on the CPU from the caller's tables.  Errors:
- *   gfhip_last_error(NULL). */
+ *   gfhip_last_error(NULL).
+ * gfhip_spectrum_create_batched / _add_rays / _merge_batches: the batches of rays of the flux profile (above) for a
+ *   spectrum, state (G, ns, nn, 67); batches*ns*nn <= 2^20, the LDS path up to ns*nn = 256 per batch; the same
+ *   refusals, and _merge_batches takes the batches and both cell counts of the incoming state. */
 typedef struct gfhip_spectrum gfhip_spectrum;
 
 struct gfhip_spectrum_field {
@@ -477,6 +506,12 @@ int gfhip_spectrum_info(gfhip_spectrum *spectrum, struct gfhip_flux_info *info);
 void gfhip_spectrum_destroy(gfhip_spectrum *spectrum);
 int gfhip_spectrum_npar_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
                              const double *const columns[7], size_t count, double *label, double *npar);
+gfhip_spectrum *gfhip_spectrum_create_batched(gfhip_context *ctx, const struct gfhip_flux_map *map,
+                                              const struct gfhip_spectrum_field *field, const double *sedges, size_t ns,
+                                              const double *nedges, size_t nn, size_t batches);
+int gfhip_spectrum_add_rays(gfhip_spectrum *spectrum, const uint64_t keys[8], size_t count, uint64_t first_ray);
+int gfhip_spectrum_merge_batches(gfhip_spectrum *spectrum, const int64_t *limbs, size_t batches, size_t ns, size_t nn,
+                                 uint64_t samples, uint64_t outside, uint64_t skipped);
 
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
