@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Push an ensemble of runaway electrons through the EFIT equilibrium (graph_korc/xkorc.cpp's workflow,
+graph_framework_amd/korc.py) and follow its distribution over the flux label, the pitch cosine and gamma
+(graph_framework_amd/distribution.py): every `--every` steps the particles are binned where they lie on the device, on the
+push's own stream, into a fresh exact distribution, and the snapshots are written to <output>_phase_bins.nc
+(output.write_phase_bins).
+
+    python examples/push_particles.py --particles 1000000 --steps 200 --every 50 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
+    python examples/push_particles.py --particles 100000 --dtype f64 --label-bins 16 --label-range 0,0.4 --pitch-bins 8 --gamma-bins 8 --gamma-range 1,3 --flux-tables tests/golden/efit_tables.npz
+
+The start positions are spread around the axis and the start momenta in size and pitch, seeded.  The push conserves gamma
+in a static field: the largest change of the gamma marginal between the first and the last snapshot is printed, the first
+thing to check after a run.  The pitch axis is pitch_edges(--pitch-bins): uniform on [-1, 1], its last edge just above 1.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def ensemble(count, seed):
+    """Seeded start values: positions in a box around the axis, momenta of 0.3 to 0.9 c at pitch angles all round."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    size = rng.uniform(0.3, 0.9, count)
+    cosine = rng.uniform(-1.0, 1.0, count)
+    turn = rng.uniform(0.0, 2.0*np.pi, count)
+    across = size*np.sqrt(1.0 - cosine*cosine)
+    return dict(x=rng.uniform(1.5, 1.9, count), y=rng.uniform(-0.2, 0.2, count), z=rng.uniform(-0.3, 0.3, count),
+                ux=across*np.cos(turn), uy=size*cosine, uz=across*np.sin(turn), gamma=np.zeros(count))
+
+
+def pair(text):
+    low, high = (float(v) for v in text.split(","))
+    return low, high
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--particles", type=int, default=100000)
+    parser.add_argument("--steps", type=int, default=200)
+    parser.add_argument("--every", type=int, default=50, help="steps between two snapshots of the distribution")
+    parser.add_argument("--dtype", choices=["f32", "f64"], default="f32", help="the push's state (the benchmark's is f32)")
+    parser.add_argument("--label-bins", type=int, default=16)
+    parser.add_argument("--label-range", type=pair, default=(0.0, 0.4), metavar="LOW,HIGH")
+    parser.add_argument("--pitch-bins", type=int, default=8)
+    parser.add_argument("--gamma-bins", type=int, default=8)
+    parser.add_argument("--gamma-range", type=pair, default=(1.0, 3.0), metavar="LOW,HIGH")
+    parser.add_argument("--sqrt-label", action="store_true", help="label = sqrt((psi - psi0)/span)")
+    parser.add_argument("--flux-tables", required=True, help="an .npz with efit.nc's psi and fpol tables (tests/golden/efit_tables.npz)")
+    parser.add_argument("--output", default=None, help="prefix of <output>_phase_bins.nc (default: no file)")
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--device", type=int, default=0)
+    args = parser.parse_args()
+    if args.every < 1 or args.steps < args.every:
+        parser.error("--every needs 1 <= every <= steps")
+
+    import numpy as np
+    from graph_framework_amd import korc
+    from graph_framework_amd.distribution import PhaseDistribution, pitch_edges
+    from graph_framework_amd.output import write_phase_bins
+
+    tables = dict(np.load(args.flux_tables))
+    sedges = np.linspace(*args.label_range, args.label_bins + 1)
+    pedges = pitch_edges(args.pitch_bins)
+    gedges = np.linspace(*args.gamma_range, args.gamma_bins + 1)
+    push = korc.Korc(ensemble(args.particles, args.seed), args.dtype, index=args.device)
+    push.compile()
+    push.pre_run()
+
+    snapshots, steps, done = [], [], 0
+    while done + args.every <= args.steps:
+        push.run(args.every)
+        done += args.every
+        snapshot = PhaseDistribution(push.work.context, tables, sedges, pedges, gedges, sqrt_label=args.sqrt_label)
+        push.bin(snapshot)                                   # behind the steps on the push's stream; the particles stay put
+        snapshots.append(snapshot)
+        steps.append(done)
+    bins = np.stack([snapshot.read() for snapshot in snapshots])
+    counts = [snapshot.counts() for snapshot in snapshots]
+    kind, psi0, span = snapshots[0].label_kind, snapshots[0].psi0, snapshots[0].span
+    for snapshot in snapshots:
+        snapshot.close()
+    push.work.context.close()
+
+    print("%d particles (%s), %d steps, %d snapshots on %dx%dx%d cells of %s, xi and gamma"
+          % (args.particles, args.dtype, done, len(steps), args.label_bins, args.pitch_bins, args.gamma_bins, kind))
+    for step, count, snapshot in zip(steps, counts, bins):
+        print("  step %6d: %d in a cell, %d outside, %d skipped" % (step, int(snapshot.sum()), count["outside"], count["skipped"]))
+    marginal = bins.sum(axis=(1, 2))                         # (time, ng): small integers, exact in fp64
+    print("largest change of the gamma marginal between the first and the last snapshot: %d particles of %d"
+          % (int(np.abs(marginal[-1] - marginal[0]).max()), args.particles))
+    if args.output:
+        path = args.output + "_phase_bins.nc"
+        write_phase_bins(path, bins, sedges, pedges, gedges, psi0, span, kind, steps=steps,
+                         **{name: [count[name] for count in counts] for name in ("samples", "outside", "skipped")})
+        print("wrote %s" % path)
+
+
+if __name__ == "__main__":
+    main()

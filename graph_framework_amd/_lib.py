@@ -116,6 +116,16 @@ SYMBOLS = [
     ("gfhip_spectrum_info", _I, [_P, _P]),
     ("gfhip_spectrum_destroy", None, [_P]),
     ("gfhip_spectrum_npar_host", _I, [_P, _P, _P, _S, _P, _P]),
+    ("gfhip_phase_create", _P, [_P, _P, _P, _P, _S, _P, _S, _P, _S]),
+    ("gfhip_phase_add", _I, [_P, _P, _U64, _I, _S]),
+    ("gfhip_phase_coordinates", _I, [_P, _P, _U64, _U64, _S]),
+    ("gfhip_phase_counts", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("gfhip_phase_state", _I, [_P, _P]),
+    ("gfhip_phase_merge", _I, [_P, _P, _S, _S, _S, _U64, _U64, _U64]),
+    ("gfhip_phase_read", _I, [_P, ctypes.c_double, _P]),
+    ("gfhip_phase_info", _I, [_P, _P]),
+    ("gfhip_phase_destroy", None, [_P]),
+    ("gfhip_phase_coordinates_host", _I, [_P, _P, _P, _I, _S, _P, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 

@@ -1,6 +1,6 @@
 //------------------------------------------------------------------------------
 ///  @file cell_launch.hpp
-///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip and flux_spectrum.hip.
+///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip, flux_spectrum.hip and phase_bins.hip.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_CELL_LAUNCH_HPP
 #define GFHIP_CELL_LAUNCH_HPP
@@ -64,6 +64,19 @@ void launch_spectrum_deposit_rays(const double *const *columns, const size_t fir
                                   const size_t lds_bytes, void *state, unsigned long long *counters, hipStream_t stream);
 void launch_spectrum_npar(const double *const *columns, const size_t count, const flux::map &m, const flux::field &f,
                           const double *packed, const double *fpol, double *label, double *npar, hipStream_t stream);
+
+//  phase_bins.hip.  columns: x, y, z, ux, uy, uz, gamma and the weight (null: every particle deposits 1.0), all float
+//  when is_f32 and all double otherwise; edges: the n[0] + 1 of the label, the n[1] + 1 of xi, the n[2] + 1 of gamma,
+//  scale[a] = n[a]/(last edge - first edge); the cell of (is, ip, ig) is (is*n[1] + ip)*n[2] + ig.
+hipError_t phase_prepare();
+void launch_phase_deposit(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
+                          const flux::map &m, const flux::field &f, const double *packed, const double *fpol,
+                          const double *edges, const size_t *n, const double *scale, const bool is_private,
+                          const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                          void *state, unsigned long long *counters, hipStream_t stream);
+void launch_phase_coordinates(const void *const *columns, const bool is_f32, const size_t count, const flux::map &m,
+                              const flux::field &f, const double *packed, const double *fpol, double *label, double *pitch,
+                              hipStream_t stream);
 
 }  // namespace gfhip
 

@@ -36,6 +36,13 @@
 ///      den  = sqrt((gZ*gZ + f*f) + gR*gR)
 ///      npar = (c*(num/den))/w
 ///
+///  The pitch cosine of a particle (x, y, z, ux, uy, uz), for phase_bins.hip: num and den as above with u in place of k,
+///
+///      cosine = num/den
+///      uu = (ux*ux + uy*uy) + uz*uz
+///      p  = sqrt(uu)
+///      xi = cosine/p;   if (xi > 1) xi = 1;   if (xi < -1) xi = -1        (comparisons: a NaN, as of u = 0, stays one)
+///
 ///  No integer conversion of a NaN or of a value out of range is reached.  Which NaN an operation gives is not IEEE's
 ///  business and differs between processors: the label and npar of a sample leave as canonical(), so that the bits are
 ///  the same everywhere.
@@ -193,9 +200,9 @@ GFHIP_HD double canonical(const double v) {
     return v == v ? v : __builtin_nan("");
 }
 
-//  N from the pieces above.
-GFHIP_HD double npar_of(const field &f, const double x, const double y, const double r, const double kx, const double ky,
-                        const double kz, const double w, const double gr, const double gz, const double fpol) {
+//  cosine = num/den of the lines above: (k.B)/|B|, the component of (kx, ky, kz) along the field.
+GFHIP_HD double cosine_of(const double x, const double y, const double r, const double kx, const double ky, const double kz,
+                          const double gr, const double gz, const double fpol) {
 #ifdef __clang__
 #pragma clang fp contract(off)
 #endif
@@ -214,8 +221,37 @@ GFHIP_HD double npar_of(const field &f, const double x, const double y, const do
     const double ff = fpol*fpol;
     const double grgr = gr*gr;
     const double den = sqrt((gzgz + ff) + grgr);
-    const double cosine = num/den;
+    return num/den;
+}
+
+//  N from the pieces above.
+GFHIP_HD double npar_of(const field &f, const double x, const double y, const double r, const double kx, const double ky,
+                        const double kz, const double w, const double gr, const double gz, const double fpol) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double cosine = cosine_of(x, y, r, kx, ky, kz, gr, gz, fpol);
     return canonical((f.c*cosine)/w);
+}
+
+//  The pitch cosine xi = (u.B)/(|u||B|) of a particle with momentum (ux, uy, uz), for phase_bins.hip.  The quotient of
+//  a parallel u comes out a few 1e-16 above 1 in a third of the cases: it is clamped, by comparisons, so that a NaN
+//  (u = 0: 0/0) stays one.
+GFHIP_HD double pitch_of(const double x, const double y, const double r, const double ux, const double uy, const double uz,
+                         const double gr, const double gz, const double fpol) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double cosine = cosine_of(x, y, r, ux, uy, uz, gr, gz, fpol);
+    const double uxux = ux*ux;
+    const double uyuy = uy*uy;
+    const double uzuz = uz*uz;
+    const double uu = (uxux + uyuy) + uzuz;
+    const double p = sqrt(uu);
+    double xi = cosine/p;
+    if (xi > 1.0) xi = 1.0;
+    if (xi < -1.0) xi = -1.0;
+    return canonical(xi);
 }
 
 //  The quadrature of the flux volumes (include/gf_hip.h): every table cell cut into sub x sub sub-cells, point

@@ -1,8 +1,8 @@
 //------------------------------------------------------------------------------
 ///  @file flux_sums.hpp
-///  @brief What the deposit kernels of flux_profile.hip and flux_spectrum.hip share (device side): the label of a point
-///  from the repacked psi tables, a workgroup's sums, private in LDS or global, and the deposit of their batched
-///  variants, one batch of rays (ray_batches.hpp) at a time.
+///  @brief What the deposit kernels of flux_profile.hip, flux_spectrum.hip and phase_bins.hip share (device side): the
+///  label of a point from the repacked psi tables, a workgroup's sums, private in LDS or global, and the deposit of the
+///  batched variants, one batch of rays (ray_batches.hpp) at a time.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_FLUX_SUMS_HPP
 #define GFHIP_FLUX_SUMS_HPP

@@ -140,6 +140,7 @@ struct gfhip_context {
     std::vector<std::unique_ptr<gfhip_bins>> bins;     // deposition grids (gfhip_bins_create), until gfhip_bins_destroy
     std::vector<std::unique_ptr<gfhip_flux>> fluxes;   // flux profiles (gfhip_flux_create), until gfhip_flux_destroy
     std::vector<std::unique_ptr<gfhip_spectrum>> spectra;      // spectra (gfhip_spectrum_create), until gfhip_spectrum_destroy
+    std::vector<std::unique_ptr<gfhip_phase>> phases;          // distributions (gfhip_phase_create), until gfhip_phase_destroy
     std::string error;
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
@@ -256,6 +257,15 @@ struct gfhip_spectrum : flux_cells {
     gfhip::flux::field field = {};
     size_t ns = 0, nn = 0;
     double sscale = 0.0, nscale = 0.0;
+    device_ptr<double> fpol;
+};
+
+//  A distribution of particles over the flux label, the pitch cosine and gamma: cell (is*np + ip)*ng + ig; the three
+//  axes' edges one after the other; fpol as [interval][4].
+struct gfhip_phase : flux_cells {
+    gfhip::flux::field field = {};
+    size_t n[3] = {0, 0, 0};
+    double scale[3] = {0.0, 0.0, 0.0};
     device_ptr<double> fpol;
 };
 
@@ -1977,6 +1987,19 @@ static const char *spectrum_field_of(const gfhip_spectrum_field *given, gfhip::f
     return nullptr;
 }
 
+//  The four fpol tables as [interval][4]: a lane's coefficients are one 32-byte line.  False: no memory.
+static bool fpol_lines(const gfhip_spectrum_field *field, std::vector<double> &lines) {
+    try {
+        lines.resize(static_cast<size_t> (field->numpsi)*4);
+    } catch (const std::bad_alloc &) {
+        return false;
+    }
+    for (size_t k = 0; k < 4; k++) {
+        for (size_t q = 0; q < field->numpsi; q++) lines[q*4 + k] = field->fpol[k][q];
+    }
+    return true;
+}
+
 //  batch_count: 0 for gfhip_spectrum_create.
 static gfhip_spectrum *spectrum_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
                                        const double *sedges, const size_t ns, const double *nedges, const size_t nn,
@@ -2008,16 +2031,10 @@ static gfhip_spectrum *spectrum_create(gfhip_context *ctx, const gfhip_flux_map 
     s->nscale = static_cast<double> (nn)/(nedges[nn] - nedges[0]);
     std::vector<double> edges(sedges, sedges + ns + 1);
     edges.insert(edges.end(), nedges, nedges + nn + 1);
-//  [interval][4]: a lane's fpol coefficients are one 32-byte line.
     std::vector<double> lines;
-    try {
-        lines.resize(static_cast<size_t> (field->numpsi)*4);
-    } catch (const std::bad_alloc &) {
+    if (!fpol_lines(field, lines)) {
         ctx->fail("a spectrum's fpol tables do not fit the host's memory");
         return nullptr;
-    }
-    for (size_t k = 0; k < 4; k++) {
-        for (size_t q = 0; q < field->numpsi; q++) lines[q*4 + k] = field->fpol[k][q];
     }
     if (s->create(ctx, map, ns*nn, edges, gfhip::spectrum_prepare, batch_count) ||
         ctx->check(allocate(s->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
@@ -2168,6 +2185,198 @@ extern "C" int gfhip_spectrum_npar_host(const gfhip_flux_map *map, const gfhip_s
         for (size_t k = 0; k < 4; k++) cubic[k] = field->fpol[k][q];
         npar[s] = gfhip::flux::npar_of(f, x, y, gfhip::flux::radius_of(x, y), columns[3][s], columns[4][s], columns[5][s],
                                        columns[6][s], gr, gz, gfhip::flux::fpol_of(cubic, tp));
+    }
+    return 0;
+}
+
+//  Distributions of particles over the flux label, the pitch cosine and gamma (phase_bins.hip, flux_label.hpp).  At most
+//  4096 cells per axis and 2^20 in all (536 B each: 563 MB of state); the three axes' edges are staged in LDS on both
+//  paths.
+static const size_t phase_cell_limit = static_cast<size_t> (1) << 20;
+
+//  The scalars of a distribution's field: a spectrum's, whose c takes no part here.
+static const char *phase_field_of(const gfhip_spectrum_field *given, gfhip::flux::field &f) {
+    gfhip_spectrum_field without_c = *given;
+    without_c.c = 1.0;
+    return spectrum_field_of(&without_c, f);
+}
+
+//  The label and the pitch cosine of one particle from the caller's 16 + 4 tables, both NaN outside the map.
+static void phase_point(const gfhip::flux::map &m, const gfhip::flux::field &f, const gfhip_flux_map *map,
+                        const gfhip_spectrum_field *field, const double x, const double y, const double z, const double ux,
+                        const double uy, const double uz, double &label, double &pitch) {
+    const size_t table = static_cast<size_t> (map->numr*map->numz);
+    double tr, tz, tp, gr, gz, c[16], cubic[4];
+    const long long at = gfhip::flux::locate(m, x, y, z, tr, tz);
+    if (at < 0) {
+        label = pitch = std::numeric_limits<double>::quiet_NaN();
+        return;
+    }
+    for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
+    const double psi = gfhip::flux::psi_gradient(m, c, tr, tz, gr, gz);
+    label = gfhip::flux::canonical(gfhip::flux::label_of(m, psi));
+    const int q = gfhip::flux::fpol_interval(f, psi, tp);
+    for (size_t k = 0; k < 4; k++) cubic[k] = field->fpol[k][q];
+    pitch = gfhip::flux::pitch_of(x, y, gfhip::flux::radius_of(x, y), ux, uy, uz, gr, gz, gfhip::flux::fpol_of(cubic, tp));
+}
+
+extern "C" gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                           const double *sedges, size_t ns, const double *pedges, size_t np,
+                                           const double *gedges, size_t ng) {
+    if (!ctx) return nullptr;
+    if (!map || !field || !sedges || !pedges || !gedges) {
+        ctx->fail("a distribution needs a map, a field and three edge arrays");
+        return nullptr;
+    }
+    const double *axes[3] = {sedges, pedges, gedges};
+    const size_t n[3] = {ns, np, ng};
+    std::vector<double> edges;
+    size_t cells = 1;
+    for (int a = 0; a < 3; a++) {
+        if (n[a] < 1 || n[a] > flux_cell_limit) {
+            ctx->fail("a distribution has 1 to 4096 cells per axis (at least two edges)");
+            return nullptr;
+        }
+        if (!edges_increase(axes[a], n[a])) {
+            ctx->fail("the edges of a distribution must be finite and strictly increasing");
+            return nullptr;
+        }
+        edges.insert(edges.end(), axes[a], axes[a] + n[a] + 1);
+        cells *= n[a];                                 // at most 2^36
+    }
+    if (cells > phase_cell_limit) {
+        ctx->fail("a distribution has at most 2^20 cells (536 B each)");
+        return nullptr;
+    }
+    std::unique_ptr<gfhip_phase> p(new gfhip_phase);
+    if (const char *refused = phase_field_of(field, p->field)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    for (int a = 0; a < 3; a++) {
+        p->n[a] = n[a];
+        p->scale[a] = static_cast<double> (n[a])/(axes[a][n[a]] - axes[a][0]);
+    }
+    std::vector<double> lines;
+    if (!fpol_lines(field, lines)) {
+        ctx->fail("a distribution's fpol tables do not fit the host's memory");
+        return nullptr;
+    }
+    if (p->create(ctx, map, cells, edges, gfhip::phase_prepare) ||
+        ctx->check(allocate(p->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
+        ctx->check(hipMemcpy(p->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
+        return nullptr;
+    }
+    ctx->phases.push_back(std::move(p));
+    return ctx->phases.back().get();
+}
+
+extern "C" void gfhip_phase_destroy(gfhip_phase *p) {
+    destroy_in(&gfhip_context::phases, p);
+}
+
+//  `used` real buffers of ONE type, fp32 or fp64, of at least `count` elements, or the message; nothing is enqueued.
+static int particle_columns(gfhip_context *ctx, const uint64_t *keys, const size_t used, const size_t count,
+                            const void **columns, bool &is_f32) {
+    uint32_t dtype = 0;
+    for (size_t c = 0; c < used; c++) {
+        const buffer *found = find_buffer(ctx, keys[c]);
+        if (!found) return 1;
+        if (found->dtype != GFIR_F64 && found->dtype != GFIR_F32) return ctx->fail("a distribution takes fp32 or fp64 buffers");
+        if (c && found->dtype != dtype) return ctx->fail("a distribution takes buffers of one type, all fp32 or all fp64");
+        if (found->count < count) return ctx->fail("a distribution buffer is shorter than the particle count");
+        dtype = found->dtype;
+        columns[c] = found->pointer;
+    }
+    is_f32 = dtype == GFIR_F32;
+    return 0;
+}
+
+extern "C" int gfhip_phase_add(gfhip_phase *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count) {
+    if (!p) return 1;
+    if (!keys) return p->ctx->fail("gfhip_phase_add needs its 7 keys");
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
+    const void *columns[8] = {};
+    bool is_f32 = false;
+    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32)) return 1;
+    return p->add(count, [&](const size_t first, const size_t piece) {
+        gfhip::launch_phase_deposit(columns, is_f32, first, piece, p->map, p->field, p->packed.get(), p->fpol.get(),
+                                    p->edges.get(), p->n, p->scale, p->is_private, p->block, p->max_workgroups, p->lds_bytes,
+                                    p->state.get(), p->counters.get(), p->ctx->stream);
+    });
+}
+
+extern "C" int gfhip_phase_coordinates(gfhip_phase *p, const uint64_t keys[7], uint64_t label_key, uint64_t pitch_key, size_t count) {
+    if (!p) return 1;
+    gfhip_context *ctx = p->ctx;
+    if (!keys) return ctx->fail("gfhip_phase_coordinates needs its 7 keys");
+    const void *columns[8] = {};
+    bool is_f32 = false;
+    if (particle_columns(ctx, keys, 7, count, columns, is_f32)) return 1;
+    double *out[2];
+    if (fp64_columns(ctx, "a distribution's label and pitch", {label_key, pitch_key}, count, out)) return 1;
+    if (enter(ctx)) return 1;
+    gfhip::launch_phase_coordinates(columns, is_f32, count, p->map, p->field, p->packed.get(), p->fpol.get(), out[0], out[1],
+                                    ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "phase coordinates launch");
+    return 0;
+}
+
+extern "C" int gfhip_phase_counts(gfhip_phase *p, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
+    return p ? p->counts(samples, outside, skipped) : 1;
+}
+
+extern "C" int gfhip_phase_state(gfhip_phase *p, int64_t *limbs) {
+    if (!p) return 1;
+    if (!limbs) return p->ctx->fail("gfhip_phase_state needs a destination");
+    return p->state_to(limbs);
+}
+
+extern "C" int gfhip_phase_merge(gfhip_phase *p, const int64_t *limbs, size_t ns, size_t np, size_t ng, uint64_t samples,
+                                 uint64_t outside, uint64_t skipped) {
+    if (!p) return 1;
+    if (!limbs) return p->ctx->fail("gfhip_phase_merge needs a state");
+    if (ns != p->n[0] || np != p->n[1] || ng != p->n[2]) return p->ctx->fail("merge: a distribution of another shape");
+    return p->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_phase_read(gfhip_phase *p, double divisor, double *values) {
+    if (!p) return 1;
+    if (!values) return p->ctx->fail("gfhip_phase_read needs a destination");
+    return p->read(divisor, values);
+}
+
+//  Not through enter(): as gfhip_flux_info.
+extern "C" int gfhip_phase_info(gfhip_phase *p, struct gfhip_flux_info *info) {
+    if (!p) return 1;
+    if (!info) return p->ctx->fail("gfhip_phase_info needs a destination");
+    p->info_to(info);
+    return 0;
+}
+
+//  Host side, no device: flux_label.hpp on the caller's 16 + 4 tables.
+extern "C" int gfhip_phase_coordinates_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                            const void *const columns[7], int is_f32, size_t count, double *label, double *pitch) {
+    bool complete = map && field && columns && ((label && pitch) || !count);
+    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
+    if (!complete) {
+        creation_error = "gfhip_phase_coordinates_host needs a map, a field, seven columns and two destinations";
+        return 1;
+    }
+    gfhip::flux::map m;
+    gfhip::flux::field f;
+    const char *refused = flux_map_of(map, m);
+    if (!refused) refused = phase_field_of(field, f);
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    for (size_t s = 0; s < count; s++) {
+        double v[6];
+        for (int k = 0; k < 6; k++) {
+            v[k] = is_f32 ? static_cast<double> (static_cast<const float *> (columns[k])[s]) : static_cast<const double *> (columns[k])[s];
+        }
+        phase_point(m, f, map, field, v[0], v[1], v[2], v[3], v[4], v[5], label[s], pitch[s]);
     }
     return 0;
 }

@@ -91,6 +91,14 @@ class Korc:
     def wait(self):
         self.work.wait()
 
+    def bin(self, distribution, weight=None):
+        """Bin the particles as they lie on the device into `distribution` (a distribution.PhaseDistribution made on
+        self.work.context): enqueued on the push's stream behind the steps run so far, no synchronisation, no copy.
+        weight: the key of a buffer of this context with the push's dtype; every particle counts 1.0 without one."""
+        if distribution.context is not self.work.context:
+            raise ValueError("the distribution must be created on the push's context (push.work.context)")
+        distribution.add(*PARTICLE, self.num_particles, weight=weight)
+
     def sync_host(self):
         for k in PARTICLE:
             self.work.copy_to_host(k, self.host[k])

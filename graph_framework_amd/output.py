@@ -479,6 +479,35 @@ def write_spectrum_bins(path, bins, sbins, nbins, psi0, span, label="s", c=1.0, 
     file.close()
 
 
+def write_phase_bins(path, bins, sbins, pbins, gbins, psi0, span, label="s", steps=None, samples=None, outside=None,
+                     skipped=None):
+    """phase_bins.nc, the snapshots of a particle distribution (distribution.py): dimensions time, ns, nsp, np, npp, ng,
+    ngp; f8 variables bins(time, ns, np, ng), sbins(nsp), pbins(npp) and gbins(ngp), the edges in the label, the pitch
+    cosine and gamma; steps(time), the push's step count at every snapshot, and samples(time), outside(time),
+    skipped(time), what became of its particles (f8, as every variable; zeros when not given); psi0 and span (f8) and the
+    label kind as global attributes.  A single (ns, np, ng) array is one snapshot."""
+    bins = np.asarray(bins)
+    if bins.ndim == 3:
+        bins = bins[None]
+    if bins.ndim != 4:
+        raise ValueError("a distribution's bins are (time, ns, np, ng)")
+    file = BinsFile(path)
+    file.create_dimension("time", bins.shape[0])
+    for name, length in zip(("ns", "np", "ng"), bins.shape[1:]):
+        file.create_dimension(name, length)
+        file.create_dimension(name + "p", length + 1)
+    file.write_variable("bins", bins, ("time", "ns", "np", "ng"))
+    for name, edges, dimension in (("sbins", sbins, "nsp"), ("pbins", pbins, "npp"), ("gbins", gbins, "ngp")):
+        file.write_variable(name, np.asarray(edges).reshape(-1), (dimension,))
+    for name, values in (("steps", steps), ("samples", samples), ("outside", outside), ("skipped", skipped)):
+        values = np.zeros(bins.shape[0]) if values is None else np.asarray(values, dtype=np.float64).reshape(-1)
+        file.write_variable(name, values, ("time",))
+    file.float64_attribute("psi0", psi0)
+    file.float64_attribute("span", span)
+    file.text_attribute("label", label)
+    file.close()
+
+
 #  Variables of the reference's ray files, solver.hpp:338-346.
 RAY_VARIABLES = (("time", "t"), ("residual", "residual"), ("w", "w"), ("x", "x"), ("y", "y"), ("z", "z"),
                  ("kx", "kx"), ("ky", "ky"), ("kz", "kz"))

@@ -513,6 +513,56 @@ int gfhip_spectrum_add_rays(gfhip_spectrum *spectrum, const uint64_t keys[8], si
 int gfhip_spectrum_merge_batches(gfhip_spectrum *spectrum, const int64_t *limbs, size_t batches, size_t ns, size_t nn,
                                  uint64_t samples, uint64_t outside, uint64_t skipped);
 
+/* Distribution of particles over the flux label, the pitch cosine and gamma: the particles of a push (x, y, z, ux,
+ * uy, uz, gamma) binned where they lie on the device, every cell the EXACT sum of its particles' weights (state shape
+ * (ns, np, ng, 67), cell (is, ip, ig) at (is*np + ip)*ng + ig).
+ *
+ * The seven columns are fp32 or fp64; an fp32 value is widened to fp64 first, which is exact, and everything after
+ * that is the fp64 arithmetic of csrc/flux_label.hpp, every line one IEEE fp64 operation in this order, nothing fused.
+ * The label, gR, gZ and f are those of the spectrum above; with u in place of k,
+ *     a = ux*x + uy*y;  b = uy*x - ux*y
+ *     num = (a*gZ + b*f)/R - uz*gR;  den = sqrt((gZ*gZ + f*f) + gR*gR);  cosine = num/den
+ *     uu = (ux*ux + uy*uy) + uz*uz;  p = sqrt(uu);  xi = cosine/p
+ *     if (xi > 1) xi = 1;  if (xi < -1) xi = -1        (comparisons: a NaN stays a NaN)
+ * The clamp is needed: for u parallel to B the quotient comes out up to 7e-16 above 1 in a third of the cases.  u = 0
+ * gives 0/0, a NaN.  gamma is read from its column as it is.  A NaN label or xi is handed out as the quiet NaN without
+ * payload.
+ * A particle belongs to cell (is, ip, ig) iff sedges[is] <= label < sedges[is+1], pedges[ip] <= xi < pedges[ip+1] and
+ * gedges[ig] <= gamma < gedges[ig+1].  The last edge of an axis is outside it: pitch edges that should hold xi = 1
+ * end above 1 (the Python helper pitch_edges(n) ends at nextafter(1, 2)).  It deposits its weight, an eighth column
+ * of the same type, or 1.0 without one.  `outside`: off the map, off any axis, or a NaN label, xi or gamma; `skipped`:
+ * inside with a NaN or infinite weight.  There are no batches of rays here: particles are no Monte-Carlo rays.
+ *
+ * gfhip_phase_create: as gfhip_spectrum_create with three edge arrays; the field's c is ignored.  Refused: what
+ *   gfhip_flux_create refuses for the map and gfhip_spectrum_create for the field (c apart); an axis outside 1-4096
+ *   cells (fewer than two edges); ns*np*ng > 2^20; edges not finite or not strictly increasing.  Up to 256 cells
+ *   (ns*np*ng) every workgroup sums its deposits in LDS, unless the map sets GFHIP_FLUX_NO_PRIVATE_SUMS; the state is
+ *   the same bytes either way, and for fp32 and fp64 columns of equal values.
+ * gfhip_phase_add: keys = x, y, z, ux, uy, uz, gamma, and weight_key when has_weight is non-zero: context buffers of
+ *   at least `count` elements, all fp32 or all fp64 (the type comes from the buffers).  Asynchronous on the context's
+ *   stream; launches of at most 2^30 particles, normalised by the rule of gfhip_flux_add.  Refused before any launch:
+ *   an unknown key, a complex or mixed type, a buffer shorter than `count`.
+ * gfhip_phase_coordinates: the label and xi of `count` particles into two fp64 buffers, both NaN outside the map.
+ * gfhip_phase_counts / _state / _read / _info / _destroy: as the spectrum's; _merge takes the three cell counts of the
+ *   incoming state and refuses another shape.
+ * gfhip_phase_coordinates_host: no device, no context; the same lines on the CPU from the caller's tables, the seven
+ *   columns float when is_f32 is non-zero and double otherwise.  Errors: gfhip_last_error(NULL). */
+typedef struct gfhip_phase gfhip_phase;
+
+gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                                const double *sedges, size_t ns, const double *pedges, size_t np, const double *gedges, size_t ng);
+int gfhip_phase_add(gfhip_phase *phase, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count);
+int gfhip_phase_coordinates(gfhip_phase *phase, const uint64_t keys[7], uint64_t label_key, uint64_t pitch_key, size_t count);
+int gfhip_phase_counts(gfhip_phase *phase, uint64_t *samples, uint64_t *outside, uint64_t *skipped);
+int gfhip_phase_state(gfhip_phase *phase, int64_t *limbs);
+int gfhip_phase_merge(gfhip_phase *phase, const int64_t *limbs, size_t ns, size_t np, size_t ng, uint64_t samples,
+                      uint64_t outside, uint64_t skipped);
+int gfhip_phase_read(gfhip_phase *phase, double divisor, double *values);
+int gfhip_phase_info(gfhip_phase *phase, struct gfhip_flux_info *info);
+void gfhip_phase_destroy(gfhip_phase *phase);
+int gfhip_phase_coordinates_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                                 const void *const columns[7], int is_f32, size_t count, double *label, double *pitch);
+
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
  * Non-zero for a NaN or an infinity among the values (gfhip_last_error(NULL)). */
