@@ -3,10 +3,13 @@
 graph_framework_amd/korc.py) and follow its distribution over the flux label, the pitch cosine and gamma
 (graph_framework_amd/distribution.py): every `--every` steps the particles are binned where they lie on the device, on the
 push's own stream, into a fresh exact distribution, and the snapshots are written to <output>_phase_bins.nc
-(output.write_phase_bins).
+(output.write_phase_bins).  With --loss-limit the particles are also tracked for their first exit through the flux surface
+of that label (graph_framework_amd/confinement.py) at every snapshot: the snapshots then hold the confined particles
+only, the confined fraction is printed per snapshot, and the losses over R, z and gamma go to <output>_loss_bins.nc.
 
     python examples/push_particles.py --particles 1000000 --steps 200 --every 50 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
     python examples/push_particles.py --particles 100000 --dtype f64 --label-bins 16 --label-range 0,0.4 --pitch-bins 8 --gamma-bins 8 --gamma-range 1,3 --flux-tables tests/golden/efit_tables.npz
+    python examples/push_particles.py --particles 1000000 --loss-limit 0.06 --loss-bins 32,32,8 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
 
 The start positions are spread around the axis and the start momenta in size and pitch, seeded.  The push conserves gamma
 in a static field: the largest change of the gamma marginal between the first and the last snapshot is printed, the first
@@ -37,6 +40,16 @@ def pair(text):
     return low, high
 
 
+def triple(text):
+    nr, nz, ng = (int(v) for v in text.split(","))
+    return nr, nz, ng
+
+
+def box(text):
+    rlo, rhi, zlo, zhi = (float(v) for v in text.split(","))
+    return rlo, rhi, zlo, zhi
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--particles", type=int, default=100000)
@@ -49,6 +62,11 @@ def main():
     parser.add_argument("--gamma-bins", type=int, default=8)
     parser.add_argument("--gamma-range", type=pair, default=(1.0, 3.0), metavar="LOW,HIGH")
     parser.add_argument("--sqrt-label", action="store_true", help="label = sqrt((psi - psi0)/span)")
+    parser.add_argument("--loss-limit", type=float, default=None, metavar="L",
+                        help="track first exits: a particle is lost once its label is not below L")
+    parser.add_argument("--loss-bins", type=triple, default=(16, 16, 8), metavar="NR,NZ,NG", help="cells of the loss footprint")
+    parser.add_argument("--loss-box", type=box, default=None, metavar="RLO,RHI,ZLO,ZHI",
+                        help="the footprint's extent in R and z (default: the map's)")
     parser.add_argument("--flux-tables", required=True, help="an .npz with efit.nc's psi and fpol tables (tests/golden/efit_tables.npz)")
     parser.add_argument("--output", default=None, help="prefix of <output>_phase_bins.nc (default: no file)")
     parser.add_argument("--seed", type=int, default=0)
@@ -60,7 +78,7 @@ def main():
     import numpy as np
     from graph_framework_amd import korc
     from graph_framework_amd.distribution import PhaseDistribution, pitch_edges
-    from graph_framework_amd.output import write_phase_bins
+    from graph_framework_amd.output import write_loss_bins, write_phase_bins
 
     tables = dict(np.load(args.flux_tables))
     sedges = np.linspace(*args.label_range, args.label_bins + 1)
@@ -69,13 +87,25 @@ def main():
     push = korc.Korc(ensemble(args.particles, args.seed), args.dtype, index=args.device)
     push.compile()
     push.pre_run()
+    tracker = None
+    if args.loss_limit is not None:
+        from graph_framework_amd.confinement import Confinement
+        numr, numz = tables["psi_c00"].shape
+        rmin, dr, zmin, dz = (float(tables[k]) for k in ("rmin", "dr", "zmin", "dz"))
+        rlo, rhi, zlo, zhi = args.loss_box or (rmin, rmin + numr*dr, zmin, zmin + numz*dz)
+        nr, nz, ng = args.loss_bins
+        tracker = Confinement(push.work.context, tables, np.linspace(rlo, rhi, nr + 1), np.linspace(zlo, zhi, nz + 1),
+                              np.linspace(*args.gamma_range, ng + 1), args.particles, args.dtype, limit=args.loss_limit,
+                              sqrt_label=args.sqrt_label, capacity=args.steps//args.every)
 
     snapshots, steps, done = [], [], 0
     while done + args.every <= args.steps:
         push.run(args.every)
         done += args.every
         snapshot = PhaseDistribution(push.work.context, tables, sedges, pedges, gedges, sqrt_label=args.sqrt_label)
-        push.bin(snapshot)                                   # behind the steps on the push's stream; the particles stay put
+        if tracker is not None:
+            push.track(tracker)                              # settles the particles that have left since the last snapshot
+        push.bin(snapshot, weight=tracker.alive_key if tracker is not None else None)        # behind the steps on the push's stream; the particles stay put
         snapshots.append(snapshot)
         steps.append(done)
     bins = np.stack([snapshot.read() for snapshot in snapshots])
@@ -83,6 +113,9 @@ def main():
     kind, psi0, span = snapshots[0].label_kind, snapshots[0].psi0, snapshots[0].span
     for snapshot in snapshots:
         snapshot.close()
+    if tracker is not None:
+        history, lost, loss_counts = tracker.history(), tracker.read(), tracker.counts()
+        tracker.close()
     push.work.context.close()
 
     print("%d particles (%s), %d steps, %d snapshots on %dx%dx%d cells of %s, xi and gamma"
@@ -92,6 +125,16 @@ def main():
     marginal = bins.sum(axis=(1, 2))                         # (time, ng): small integers, exact in fp64
     print("largest change of the gamma marginal between the first and the last snapshot: %d particles of %d"
           % (int(np.abs(marginal[-1] - marginal[0]).max()), args.particles))
+    if tracker is not None:
+        print("first exits through %s = %g, on %dx%dx%d cells of R, z and gamma:" % ((kind, args.loss_limit) + tracker.shape))
+        for step, newly, confined in zip(history["steps"], history["newly_lost"], history["confined"]):
+            print("  step %6d: %d newly lost, confined fraction %.6f" % (step, newly, confined/args.particles))
+        print("  %d lost in all, %d of them outside the footprint's cells" % (loss_counts["samples"], loss_counts["outside"]))
+        if args.output:
+            path = args.output + "_loss_bins.nc"
+            write_loss_bins(path, lost, tracker.redges, tracker.zedges, tracker.gedges, tracker.limit, tracker.psi0, tracker.span,
+                            kind, **history, **loss_counts)
+            print("wrote %s" % path)
     if args.output:
         path = args.output + "_phase_bins.nc"
         write_phase_bins(path, bins, sedges, pedges, gedges, psi0, span, kind, steps=steps,

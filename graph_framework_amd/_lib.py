@@ -126,6 +126,18 @@ SYMBOLS = [
     ("gfhip_phase_info", _I, [_P, _P]),
     ("gfhip_phase_destroy", None, [_P]),
     ("gfhip_phase_coordinates_host", _I, [_P, _P, _P, _I, _S, _P, _P]),
+    ("gfhip_confine_create", _P, [_P, _P, ctypes.c_double, _P, _S, _P, _S, _P, _S, _S, _I, _U64, _S]),
+    ("gfhip_confine_check", _I, [_P, _P, _U64, _I, _U64, _U64, _I, _U32]),
+    ("gfhip_confine_lost_steps", _I, [_P, _P]),
+    ("gfhip_confine_history", _I, [_P, _P, _P, ctypes.POINTER(_S)]),
+    ("gfhip_confine_counts", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("gfhip_confine_state", _I, [_P, _P]),
+    ("gfhip_confine_merge", _I, [_P, _P, _S, _S, _S, _U64, _U64, _U64]),
+    ("gfhip_confine_read", _I, [_P, ctypes.c_double, _P]),
+    ("gfhip_confine_info", _I, [_P, _P]),
+    ("gfhip_confine_destroy", None, [_P]),
+    ("gfhip_confine_check_host", _I, [_P, ctypes.c_double, _P, _S, _P, _S, _P, _S, _P, _I, _S, _U32, _P, _P, _P, _P,
+                                      ctypes.POINTER(_U64), _P, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 

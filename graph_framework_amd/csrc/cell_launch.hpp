@@ -1,12 +1,13 @@
 //------------------------------------------------------------------------------
 ///  @file cell_launch.hpp
-///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip, flux_spectrum.hip and phase_bins.hip.
+///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip, flux_spectrum.hip, phase_bins.hip and confinement.hip.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_CELL_LAUNCH_HPP
 #define GFHIP_CELL_LAUNCH_HPP
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #include "flux_label.hpp"
 
@@ -77,6 +78,20 @@ void launch_phase_deposit(const void *const *columns, const bool is_f32, const s
 void launch_phase_coordinates(const void *const *columns, const bool is_f32, const size_t count, const flux::map &m,
                               const flux::field &f, const double *packed, const double *fpol, double *label, double *pitch,
                               hipStream_t stream);
+
+//  confinement.hip.  columns: as launch_phase_deposit's, of which x, y, z, gamma and the weight are read; alive: the
+//  tracker's own column of the same type; edges: the n[0] + 1 of R, the n[1] + 1 of z, the n[2] + 1 of gamma; the cell of
+//  (ir, iz, ig) is (ir*n[1] + iz)*n[2] + ig.  lost_step, alive and the exit buffers (both null without them) are indexed
+//  by particle, first .. first + count; newly_lost is the entry of this check.  Always the global path's launch shape.
+void launch_confinement_check(const void *const *columns, void *alive, const bool is_f32, const size_t first, const size_t count,
+                              const flux::map &m, const double *packed, const double limit, const double *edges,
+                              const size_t *n, const double *scale, const uint32_t step, uint32_t *lost_step, double *exit_r,
+                              double *exit_z, unsigned long long *newly_lost, const unsigned int block,
+                              const size_t max_workgroups, const size_t lds_bytes, void *state, unsigned long long *counters,
+                              hipStream_t stream);
+//  The sentinel into lost_step and 1 into alive (both null: left alone), NaN into the exit buffers (both null: none).
+void launch_confinement_reset(const size_t count, uint32_t *lost_step, void *alive, const bool is_f32, double *exit_r,
+                              double *exit_z, hipStream_t stream);
 
 }  // namespace gfhip
 

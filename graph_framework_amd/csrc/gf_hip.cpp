@@ -34,6 +34,7 @@
 #include "plan.hpp"
 
 #include "cell_launch.hpp"
+#include "confinement_host.hpp"
 #include "converge_state.hpp"
 #include "flux_label.hpp"
 #include "hand_over.hpp"
@@ -141,6 +142,7 @@ struct gfhip_context {
     std::vector<std::unique_ptr<gfhip_flux>> fluxes;   // flux profiles (gfhip_flux_create), until gfhip_flux_destroy
     std::vector<std::unique_ptr<gfhip_spectrum>> spectra;      // spectra (gfhip_spectrum_create), until gfhip_spectrum_destroy
     std::vector<std::unique_ptr<gfhip_phase>> phases;          // distributions (gfhip_phase_create), until gfhip_phase_destroy
+    std::vector<std::unique_ptr<gfhip_confine>> confines;      // trackers (gfhip_confine_create), until gfhip_confine_destroy
     std::string error;
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
@@ -267,6 +269,23 @@ struct gfhip_phase : flux_cells {
     size_t n[3] = {0, 0, 0};
     double scale[3] = {0.0, 0.0, 0.0};
     device_ptr<double> fpol;
+};
+
+//  A first-exit tracker of the particles of one push (confinement.hip): per particle lost_step and the context buffer
+//  `alive_key`; per check its step (here) and the number of particles it found lost (on the device); the footprint of
+//  the losses, cell (ir*nz + iz)*ng + ig, the three axes' edges one after the other.
+struct gfhip_confine : flux_cells {
+    double limit = 0.0;
+    size_t n[3] = {0, 0, 0};
+    double scale[3] = {0.0, 0.0, 0.0};
+    size_t count = 0, capacity = 0;
+    bool is_f32 = false;
+    uint64_t alive_key = 0;
+    device_ptr<uint32_t> lost_step;
+    device_ptr<unsigned long long> newly_lost;         // [capacity]
+    std::vector<uint32_t> steps;                       // the checks made
+    bool exit_ready = false;                           // the exit buffers of `exit_keys` hold NaN for every confined particle
+    uint64_t exit_keys[2] = {0, 0};
 };
 
 #define GFHIP_TRY(ctx, call, what) do { if ((ctx)->check((call), (what))) return 1; } while (0)
@@ -2277,14 +2296,14 @@ extern "C" void gfhip_phase_destroy(gfhip_phase *p) {
 
 //  `used` real buffers of ONE type, fp32 or fp64, of at least `count` elements, or the message; nothing is enqueued.
 static int particle_columns(gfhip_context *ctx, const uint64_t *keys, const size_t used, const size_t count,
-                            const void **columns, bool &is_f32) {
+                            const void **columns, bool &is_f32, const char *noun = "a distribution") {
     uint32_t dtype = 0;
     for (size_t c = 0; c < used; c++) {
         const buffer *found = find_buffer(ctx, keys[c]);
         if (!found) return 1;
-        if (found->dtype != GFIR_F64 && found->dtype != GFIR_F32) return ctx->fail("a distribution takes fp32 or fp64 buffers");
-        if (c && found->dtype != dtype) return ctx->fail("a distribution takes buffers of one type, all fp32 or all fp64");
-        if (found->count < count) return ctx->fail("a distribution buffer is shorter than the particle count");
+        if (found->dtype != GFIR_F64 && found->dtype != GFIR_F32) return ctx->fail(std::string(noun) + " takes fp32 or fp64 buffers");
+        if (c && found->dtype != dtype) return ctx->fail(std::string(noun) + " takes buffers of one type, all fp32 or all fp64");
+        if (found->count < count) return ctx->fail(std::string(noun) + " buffer is shorter than the particle count");
         dtype = found->dtype;
         columns[c] = found->pointer;
     }
@@ -2377,6 +2396,212 @@ extern "C" int gfhip_phase_coordinates_host(const gfhip_flux_map *map, const gfh
             v[k] = is_f32 ? static_cast<double> (static_cast<const float *> (columns[k])[s]) : static_cast<const double *> (columns[k])[s];
         }
         phase_point(m, f, map, field, v[0], v[1], v[2], v[3], v[4], v[5], label[s], pitch[s]);
+    }
+    return 0;
+}
+
+//  First-exit trackers (confinement.hip, flux_label.hpp).  The axes and the cells are a distribution's; deposits always
+//  go to the global state, so the launch shape is the global path's whatever the map's flags say.
+
+//  The three axes of a footprint checked and laid one after the other, or why they are refused.
+static const char *confine_axes_of(const double *const *axes, const size_t *n, std::vector<double> &edges, size_t &cells) {
+    cells = 1;
+    for (int a = 0; a < 3; a++) {
+        if (n[a] < 1 || n[a] > flux_cell_limit) return "a loss footprint has 1 to 4096 cells per axis (at least two edges)";
+        if (!edges_increase(axes[a], n[a])) return "the edges of a loss footprint must be finite and strictly increasing";
+        edges.insert(edges.end(), axes[a], axes[a] + n[a] + 1);
+        cells *= n[a];                                 // at most 2^36
+    }
+    if (cells > phase_cell_limit) return "a loss footprint has at most 2^20 cells (536 B each)";
+    return nullptr;
+}
+
+extern "C" gfhip_confine *gfhip_confine_create(gfhip_context *ctx, const gfhip_flux_map *map, double limit, const double *redges,
+                                               size_t nr, const double *zedges, size_t nz, const double *gedges, size_t ng,
+                                               size_t count, int is_f32, uint64_t alive_key, size_t capacity) {
+    if (!ctx) return nullptr;
+    if (!map || !redges || !zedges || !gedges) {
+        ctx->fail("a confinement tracker needs a map and three edge arrays");
+        return nullptr;
+    }
+    const double *axes[3] = {redges, zedges, gedges};
+    const size_t n[3] = {nr, nz, ng};
+    std::vector<double> edges;
+    size_t cells = 0;
+    if (const char *refused = confine_axes_of(axes, n, edges, cells)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    if (limit != limit) {
+        ctx->fail("the limit of a confinement tracker must not be NaN");
+        return nullptr;
+    }
+    if (count == 0 || capacity == 0) {
+        ctx->fail("a confinement tracker needs at least one particle and room for at least one check");
+        return nullptr;
+    }
+    gfhip_flux_map global = *map;
+    global.flags |= gfhip::flux::flag_no_private_sums;
+    std::unique_ptr<gfhip_confine> c(new gfhip_confine);
+    c->limit = limit;
+    c->count = count;
+    c->capacity = capacity;
+    c->is_f32 = is_f32 != 0;
+    c->alive_key = alive_key;
+    for (int a = 0; a < 3; a++) {
+        c->n[a] = n[a];
+        c->scale[a] = static_cast<double> (n[a])/(axes[a][n[a]] - axes[a][0]);
+    }
+    if (c->create(ctx, &global, cells, edges, nullptr) || enter(ctx) ||
+        ensure_buffer(ctx, alive_key, count, c->is_f32 ? GFIR_F32 : GFIR_F64, nullptr) ||
+        ctx->check(allocate(c->lost_step, count*sizeof(uint32_t)), "hipMalloc(lost steps)") ||
+        ctx->check(allocate(c->newly_lost, capacity*sizeof(unsigned long long)), "hipMalloc(newly lost)") ||
+        ctx->check(hipMemsetAsync(c->newly_lost.get(), 0, capacity*sizeof(unsigned long long), ctx->stream), "hipMemset(newly lost)")) {
+        return nullptr;
+    }
+    gfhip::launch_confinement_reset(count, c->lost_step.get(), find_buffer(ctx, alive_key)->pointer, c->is_f32, nullptr, nullptr,
+                                    ctx->stream);
+    if (ctx->check(hipGetLastError(), "confinement reset launch")) return nullptr;
+    ctx->confines.push_back(std::move(c));
+    return ctx->confines.back().get();
+}
+
+extern "C" void gfhip_confine_destroy(gfhip_confine *c) {
+    destroy_in(&gfhip_context::confines, c);
+}
+
+extern "C" int gfhip_confine_check(gfhip_confine *c, const uint64_t keys[7], uint64_t weight_key, int has_weight,
+                                   uint64_t exit_r_key, uint64_t exit_z_key, int has_exit, uint32_t step) {
+    if (!c) return 1;
+    gfhip_context *ctx = c->ctx;
+    if (!keys) return ctx->fail("gfhip_confine_check needs its 7 keys");
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
+    const void *columns[8] = {};
+    bool is_f32 = false;
+    if (particle_columns(ctx, all, has_weight ? 8 : 7, c->count, columns, is_f32, "a confinement tracker")) return 1;
+    if (is_f32 != c->is_f32) return ctx->fail("the columns are not of the confinement tracker's type");
+    const buffer *alive = find_buffer(ctx, c->alive_key);
+    if (!alive) return 1;
+    if (alive->dtype != (c->is_f32 ? GFIR_F32 : GFIR_F64) || alive->count < c->count) {
+        return ctx->fail("the alive buffer of a confinement tracker has been replaced by one of another type or length");
+    }
+    double *exits[2] = {nullptr, nullptr};
+    if (has_exit && fp64_columns(ctx, "a confinement tracker's exit", {exit_r_key, exit_z_key}, c->count, exits)) return 1;
+    if (step == GFHIP_CONFINED) return ctx->fail("step 0xFFFFFFFF means confined: a check cannot have it");
+    if (!c->steps.empty() && step < c->steps.back()) return ctx->fail("a check's step is below the previous check's");
+    if (c->steps.size() >= c->capacity) return ctx->fail("more checks than the confinement tracker's capacity");
+    if (enter(ctx)) return 1;
+    if (has_exit && !(c->exit_ready && c->exit_keys[0] == exit_r_key && c->exit_keys[1] == exit_z_key)) {
+        gfhip::launch_confinement_reset(c->count, nullptr, nullptr, c->is_f32, exits[0], exits[1], ctx->stream);
+        GFHIP_TRY(ctx, hipGetLastError(), "confinement reset launch");
+        c->exit_ready = true;
+        c->exit_keys[0] = exit_r_key;
+        c->exit_keys[1] = exit_z_key;
+    }
+    unsigned long long *entry = c->newly_lost.get() + c->steps.size();
+    if (c->add(c->count, [&](const size_t first, const size_t piece) {
+            gfhip::launch_confinement_check(columns, alive->pointer, c->is_f32, first, piece, c->map, c->packed.get(), c->limit,
+                                            c->edges.get(), c->n, c->scale, step, c->lost_step.get(), exits[0], exits[1], entry,
+                                            c->block, c->max_workgroups, c->lds_bytes, c->state.get(), c->counters.get(),
+                                            ctx->stream);
+        })) {
+        return 1;
+    }
+    c->steps.push_back(step);
+    return 0;
+}
+
+extern "C" int gfhip_confine_lost_steps(gfhip_confine *c, uint32_t *lost_step) {
+    if (!c) return 1;
+    gfhip_context *ctx = c->ctx;
+    if (!lost_step) return ctx->fail("gfhip_confine_lost_steps needs a destination");
+    if (enter(ctx)) return 1;
+    GFHIP_TRY(ctx, hipMemcpyAsync(lost_step, c->lost_step.get(), c->count*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpyAsync(lost steps)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return 0;
+}
+
+extern "C" int gfhip_confine_history(gfhip_confine *c, uint32_t *steps, uint64_t *newly_lost, size_t *checks) {
+    if (!c) return 1;
+    gfhip_context *ctx = c->ctx;
+    if (!checks) return ctx->fail("gfhip_confine_history needs a destination for the number of checks");
+    *checks = c->steps.size();
+    if (steps) std::copy(c->steps.begin(), c->steps.end(), steps);
+    if (newly_lost && !c->steps.empty()) {
+        if (enter(ctx)) return 1;
+        GFHIP_TRY(ctx, hipMemcpyAsync(newly_lost, c->newly_lost.get(), c->steps.size()*sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                      ctx->stream), "hipMemcpyAsync(newly lost)");
+        GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    return 0;
+}
+
+extern "C" int gfhip_confine_counts(gfhip_confine *c, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
+    return c ? c->counts(samples, outside, skipped) : 1;
+}
+
+extern "C" int gfhip_confine_state(gfhip_confine *c, int64_t *limbs) {
+    if (!c) return 1;
+    if (!limbs) return c->ctx->fail("gfhip_confine_state needs a destination");
+    return c->state_to(limbs);
+}
+
+extern "C" int gfhip_confine_merge(gfhip_confine *c, const int64_t *limbs, size_t nr, size_t nz, size_t ng, uint64_t samples,
+                                   uint64_t outside, uint64_t skipped) {
+    if (!c) return 1;
+    if (!limbs) return c->ctx->fail("gfhip_confine_merge needs a state");
+    if (nr != c->n[0] || nz != c->n[1] || ng != c->n[2]) return c->ctx->fail("merge: a loss footprint of another shape");
+    return c->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_confine_read(gfhip_confine *c, double divisor, double *values) {
+    if (!c) return 1;
+    if (!values) return c->ctx->fail("gfhip_confine_read needs a destination");
+    return c->read(divisor, values);
+}
+
+//  Not through enter(): as gfhip_flux_info.
+extern "C" int gfhip_confine_info(gfhip_confine *c, struct gfhip_flux_info *info) {
+    if (!c) return 1;
+    if (!info) return c->ctx->fail("gfhip_confine_info needs a destination");
+    c->info_to(info);
+    return 0;
+}
+
+extern "C" int gfhip_confine_check_host(const gfhip_flux_map *map, double limit, const double *redges, size_t nr,
+                                        const double *zedges, size_t nz, const double *gedges, size_t ng,
+                                        const void *const columns[8], int is_f32, size_t count, uint32_t step, uint32_t *lost_step,
+                                        void *alive, double *exit_r, double *exit_z, uint64_t *newly_lost, int64_t *limbs,
+                                        uint64_t counters[3]) {
+    bool complete = map && columns && newly_lost && ((lost_step && alive) || !count) && !exit_r == !exit_z &&
+                    (!limbs || (redges && zedges && gedges && counters));
+    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count || (k >= 3 && k <= 5) || (k == 6 && !limbs);
+    if (!complete) {
+        creation_error = "gfhip_confine_check_host needs a map, the columns x, y, z and gamma, lost_step, alive and newly_lost, "
+                         "both exit arrays or neither, and with limbs the three edge arrays and the counters";
+        return 1;
+    }
+    gfhip::flux::map m;
+    const double *axes[3] = {redges, zedges, gedges};
+    const size_t n[3] = {nr, nz, ng};
+    std::vector<double> edges;
+    size_t cells = 0;
+    const char *refused = flux_map_of(map, m);
+    if (!refused && limbs) refused = confine_axes_of(axes, n, edges, cells);
+    if (!refused && limit != limit) refused = "the limit of a confinement tracker must not be NaN";
+    if (!refused && step == GFHIP_CONFINED) refused = "step 0xFFFFFFFF means confined: a check cannot have it";
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    const size_t table = static_cast<size_t> (map->numr*map->numz);
+    if (is_f32) {
+        gfhip::confine::check_host<float> (m, map->coefficients, table, limit, axes, n, columns, count, step, lost_step, static_cast<float *> (alive), exit_r,
+                                   exit_z, newly_lost, limbs, counters);
+    } else {
+        gfhip::confine::check_host<double> (m, map->coefficients, table, limit, axes, n, columns, count, step, lost_step, static_cast<double *> (alive), exit_r,
+                                    exit_z, newly_lost, limbs, counters);
     }
     return 0;
 }

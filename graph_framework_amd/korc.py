@@ -78,6 +78,7 @@ class Korc:
                                                ["ux", "uy", "uz", "gamma"], [], self.num_particles, self.host)
         self.step_item = self.work.add_item(_item(items, "korc_step", dtype), list(PARTICLE), [],
                                             self.num_particles, self.host)
+        self.steps_done = 0                                  # steps run so far: the step number of track()
 
     def compile(self):
         self.work.compile()
@@ -87,6 +88,7 @@ class Korc:
 
     def run(self, steps=1):
         self.work.run(steps)
+        self.steps_done += int(steps)
 
     def wait(self):
         self.work.wait()
@@ -98,6 +100,18 @@ class Korc:
         if distribution.context is not self.work.context:
             raise ValueError("the distribution must be created on the push's context (push.work.context)")
         distribution.add(*PARTICLE, self.num_particles, weight=weight)
+
+    def track(self, confinement, weight=None, exit=None):
+        """Examine the particles as they lie on the device for first exits (a confinement.Confinement made on
+        self.work.context for this push's particle count and dtype) at step number self.steps_done: enqueued on the push's
+        stream behind the steps run so far, no synchronisation, no copy.  weight: as bin()'s; exit: the keys of two fp64
+        buffers of this context that receive R and z of the crossing.  confinement.alive_key is then a weight for bin()
+        under which lost particles drop out of the snapshot."""
+        if confinement.context is not self.work.context:
+            raise ValueError("the tracker must be created on the push's context (push.work.context)")
+        if confinement.count != self.num_particles:
+            raise ValueError("the tracker follows %d particles, the push has %d" % (confinement.count, self.num_particles))
+        confinement.check(*PARTICLE, self.steps_done, weight=weight, exit=exit)
 
     def sync_host(self):
         for k in PARTICLE:

@@ -508,6 +508,42 @@ def write_phase_bins(path, bins, sbins, pbins, gbins, psi0, span, label="s", ste
     file.close()
 
 
+def write_loss_bins(path, bins, rbins, zbins, gbins, limit, psi0, span, label="s", steps=None, newly_lost=None, confined=None,
+                    samples=0, outside=0, skipped=0):
+    """loss_bins.nc, the losses of a push (confinement.py): dimensions nr, nrp, nz, nzp, ng, ngp, check; f8 variables
+    bins(nr, nz, ng), the weight lost per cell of R, z and gamma, rbins(nrp), zbins(nzp) and gbins(ngp), the edges;
+    steps(check), newly_lost(check) and confined(check), the step of every check, the particles it found lost and those
+    confined after it (f8, as every variable; no check: one of zeros); what became of the lost particles as global integer
+    attributes; limit, psi0 and span (f8) and the label kind as global attributes."""
+    bins = np.asarray(bins)
+    if bins.ndim != 3:
+        raise ValueError("a loss footprint's bins are (nr, nz, ng)")
+    edges = [np.asarray(e, dtype=np.float64).reshape(-1) for e in (rbins, zbins, gbins)]
+    if tuple(e.size - 1 for e in edges) != bins.shape:
+        raise ValueError("bins of shape %r do not lie on %r edges" % (bins.shape, tuple(e.size for e in edges)))
+    checks = next((np.size(values) for values in (steps, newly_lost, confined) if values is not None), 1)
+    history = [np.zeros(checks) if values is None else np.asarray(values, dtype=np.float64).reshape(-1)
+               for values in (steps, newly_lost, confined)]
+    if len({values.size for values in history}) != 1 or checks == 0:
+        raise ValueError("steps, newly_lost and confined need one entry per check, and at least one check")
+    file = BinsFile(path)
+    for name, length in zip(("nr", "nz", "ng"), bins.shape):
+        file.create_dimension(name, length)
+        file.create_dimension(name + "p", length + 1)
+    file.create_dimension("check", history[0].size)
+    file.write_variable("bins", bins, ("nr", "nz", "ng"))
+    for name, values, dimension in (("rbins", edges[0], "nrp"), ("zbins", edges[1], "nzp"), ("gbins", edges[2], "ngp")):
+        file.write_variable(name, values, (dimension,))
+    for name, values in zip(("steps", "newly_lost", "confined"), history):
+        file.write_variable(name, values, ("check",))
+    _count_attributes(file, samples, outside, skipped)
+    file.float64_attribute("limit", limit)
+    file.float64_attribute("psi0", psi0)
+    file.float64_attribute("span", span)
+    file.text_attribute("label", label)
+    file.close()
+
+
 #  Variables of the reference's ray files, solver.hpp:338-346.
 RAY_VARIABLES = (("time", "t"), ("residual", "residual"), ("w", "w"), ("x", "x"), ("y", "y"), ("z", "z"),
                  ("kx", "kx"), ("ky", "ky"), ("kz", "kz"))

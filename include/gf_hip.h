@@ -563,6 +563,64 @@ void gfhip_phase_destroy(gfhip_phase *phase);
 int gfhip_phase_coordinates_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
                                  const void *const columns[7], int is_f32, size_t count, double *label, double *pitch);
 
+/* First-exit tracking of the particles of one push: which particles have left the plasma, at which step, where they
+ * crossed and at what energy, kept on the device from one check to the next (csrc/confinement.hip).
+ *
+ * Per particle the tracker holds lost_step (uint32, GFHIP_CONFINED = 0xFFFFFFFF while confined) and `alive`, a context
+ * buffer of the push's type under the caller's key, 1 while confined and 0 afterwards, which every other entry point
+ * takes as a weight.  A check with step number `step` examines the particles that are still confined, in the fixed fp64
+ * arithmetic above (fp32 columns widened first):
+ *     label = the label of (x, y, z), a NaN as the quiet NaN, NaN off the map
+ *     lost  iff  !(label < limit)       off the map, a NaN position and label == limit are all lost
+ * A particle found lost is settled once and never examined again, even if a later step carries it back inside:
+ * lost_step = step, alive = 0, exit_r = sqrt(x*x + y*y) and exit_z = z (fp64, a NaN as the quiet NaN; NaN while the
+ * particle is confined) where exit buffers are given, and its weight, or 1.0 without a weight column, is added to the
+ * EXACT cell (ir, iz, ig) of (R, z, gamma as stored): redges[ir] <= R < redges[ir+1] and so on, state shape
+ * (nr, nz, ng, 67), cell at (ir*nz + iz)*ng + ig.  newly_lost[check] counts the particles the check found lost.  The
+ * counters are those of the cells restricted to the lost: `samples` particles lost, `outside` lost but in no footprint
+ * cell, `skipped` in a cell with a NaN or infinite weight.
+ *
+ * gfhip_confine_create: `count` particles, fp32 when is_f32 is non-zero; `alive_key` is allocated with
+ *   gfhip_allocate_buffer's rule (an existing buffer must have the type and the length) and set to 1; `capacity` is the
+ *   most checks.  Refused: what gfhip_phase_create refuses for the map and the edges; nr*nz*ng > 2^20; a NaN limit;
+ *   count = 0; capacity = 0.
+ * gfhip_confine_check: keys as gfhip_phase_add's (ux, uy, uz are checked and not read); exit_r_key and exit_z_key when
+ *   has_exit is non-zero: fp64 buffers of at least `count` elements, filled with NaN when the tracker first sees them
+ *   (particles settled before that keep NaN there).  Asynchronous on the context's stream.  Refused before any launch,
+ *   with everything unchanged: an unknown key, mixed or complex columns or columns not of the tracker's type, a buffer
+ *   shorter than the tracker's count, exit buffers that are not fp64, step = GFHIP_CONFINED, a step below the previous
+ *   check's, more checks than `capacity`.
+ * gfhip_confine_lost_steps: the `count` lost_step values, after the stream has drained.
+ * gfhip_confine_history: the steps of the checks made and what each found lost, `*checks` of them (at most `capacity`;
+ *   steps and newly_lost may be NULL to ask for the number alone).
+ * gfhip_confine_counts / _state / _merge / _read / _info / _destroy: as the distribution's.
+ * gfhip_confine_check_host: no device, no context; the same lines on the CPU on the caller's arrays in place: columns
+ *   as above (columns[3..5] unread, columns[7] NULL without weights), `alive` of the columns' type, exit_r and exit_z both
+ *   NULL or both given, *newly_lost goes up by the particles found lost.  With `limbs` (nr*nz*ng*67, canonical on
+ *   return) and `counters` (3) the footprint is deposited too; with limbs = NULL the edges are not looked at.  Errors:
+ *   gfhip_last_error(NULL). */
+#define GFHIP_CONFINED 0xFFFFFFFFu
+typedef struct gfhip_confine gfhip_confine;
+
+gfhip_confine *gfhip_confine_create(gfhip_context *ctx, const struct gfhip_flux_map *map, double limit, const double *redges,
+                                    size_t nr, const double *zedges, size_t nz, const double *gedges, size_t ng, size_t count,
+                                    int is_f32, uint64_t alive_key, size_t capacity);
+int gfhip_confine_check(gfhip_confine *confine, const uint64_t keys[7], uint64_t weight_key, int has_weight, uint64_t exit_r_key,
+                        uint64_t exit_z_key, int has_exit, uint32_t step);
+int gfhip_confine_lost_steps(gfhip_confine *confine, uint32_t *lost_step);
+int gfhip_confine_history(gfhip_confine *confine, uint32_t *steps, uint64_t *newly_lost, size_t *checks);
+int gfhip_confine_counts(gfhip_confine *confine, uint64_t *samples, uint64_t *outside, uint64_t *skipped);
+int gfhip_confine_state(gfhip_confine *confine, int64_t *limbs);
+int gfhip_confine_merge(gfhip_confine *confine, const int64_t *limbs, size_t nr, size_t nz, size_t ng, uint64_t samples,
+                        uint64_t outside, uint64_t skipped);
+int gfhip_confine_read(gfhip_confine *confine, double divisor, double *values);
+int gfhip_confine_info(gfhip_confine *confine, struct gfhip_flux_info *info);
+void gfhip_confine_destroy(gfhip_confine *confine);
+int gfhip_confine_check_host(const struct gfhip_flux_map *map, double limit, const double *redges, size_t nr,
+                             const double *zedges, size_t nz, const double *gedges, size_t ng, const void *const columns[8],
+                             int is_f32, size_t count, uint32_t step, uint32_t *lost_step, void *alive, double *exit_r,
+                             double *exit_z, uint64_t *newly_lost, int64_t *limbs, uint64_t counters[3]);
+
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
  * Non-zero for a NaN or an infinity among the values (gfhip_last_error(NULL)). */
