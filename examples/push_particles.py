@@ -6,10 +6,14 @@ push's own stream, into a fresh exact distribution, and the snapshots are writte
 (output.write_phase_bins).  With --loss-limit the particles are also tracked for their first exit through the flux surface
 of that label (graph_framework_amd/confinement.py) at every snapshot: the snapshots then hold the confined particles
 only, the confined fraction is printed per snapshot, and the losses over R, z and gamma go to <output>_loss_bins.nc.
+With --moments NS every snapshot also gets the exact density, parallel current, kinetic energy and radiated power on NS
+flux surfaces of the label range (graph_framework_amd/moments.py), under the same weights; the total current and energy
+are printed per snapshot and the profiles go to <output>_moment_bins.nc, with --moments-density SUB also per volume.
 
     python examples/push_particles.py --particles 1000000 --steps 200 --every 50 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
     python examples/push_particles.py --particles 100000 --dtype f64 --label-bins 16 --label-range 0,0.4 --pitch-bins 8 --gamma-bins 8 --gamma-range 1,3 --flux-tables tests/golden/efit_tables.npz
     python examples/push_particles.py --particles 1000000 --loss-limit 0.06 --loss-bins 32,32,8 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
+    python examples/push_particles.py --particles 1000000 --moments 32 --moments-density 8 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
 
 The start positions are spread around the axis and the start momenta in size and pitch, seeded.  The push conserves gamma
 in a static field: the largest change of the gamma marginal between the first and the last snapshot is printed, the first
@@ -67,6 +71,10 @@ def main():
     parser.add_argument("--loss-bins", type=triple, default=(16, 16, 8), metavar="NR,NZ,NG", help="cells of the loss footprint")
     parser.add_argument("--loss-box", type=box, default=None, metavar="RLO,RHI,ZLO,ZHI",
                         help="the footprint's extent in R and z (default: the map's)")
+    parser.add_argument("--moments", type=int, default=None, metavar="NS",
+                        help="also bin density, current, energy and radiated power on NS surfaces of --label-range")
+    parser.add_argument("--moments-density", type=int, default=None, metavar="SUB",
+                        help="with --moments: the file also gets the surfaces' volumes (quadrature SUB) and the moments per volume")
     parser.add_argument("--flux-tables", required=True, help="an .npz with efit.nc's psi and fpol tables (tests/golden/efit_tables.npz)")
     parser.add_argument("--output", default=None, help="prefix of <output>_phase_bins.nc (default: no file)")
     parser.add_argument("--seed", type=int, default=0)
@@ -74,6 +82,8 @@ def main():
     args = parser.parse_args()
     if args.every < 1 or args.steps < args.every:
         parser.error("--every needs 1 <= every <= steps")
+    if args.moments is not None and args.moments < 1 or args.moments is None and args.moments_density is not None:
+        parser.error("--moments needs NS >= 1, and --moments-density needs --moments")
 
     import numpy as np
     from graph_framework_amd import korc
@@ -98,6 +108,11 @@ def main():
                               np.linspace(*args.gamma_range, ng + 1), args.particles, args.dtype, limit=args.loss_limit,
                               sqrt_label=args.sqrt_label, capacity=args.steps//args.every)
 
+    profiles = []
+    if args.moments is not None:
+        from graph_framework_amd.moments import MOMENTS, FluxMoments
+        from graph_framework_amd.output import write_moment_bins
+        medges = np.linspace(*args.label_range, args.moments + 1)
     snapshots, steps, done = [], [], 0
     while done + args.every <= args.steps:
         push.run(args.every)
@@ -108,11 +123,21 @@ def main():
         push.bin(snapshot, weight=tracker.alive_key if tracker is not None else None)        # behind the steps on the push's stream; the particles stay put
         snapshots.append(snapshot)
         steps.append(done)
+        if args.moments is not None:
+            profiles.append(FluxMoments(push.work.context, tables, medges, sqrt_label=args.sqrt_label))
+            push.bin(profiles[-1], weight=tracker.alive_key if tracker is not None else None)
     bins = np.stack([snapshot.read() for snapshot in snapshots])
     counts = [snapshot.counts() for snapshot in snapshots]
     kind, psi0, span = snapshots[0].label_kind, snapshots[0].psi0, snapshots[0].span
     for snapshot in snapshots:
         snapshot.close()
+    if profiles:
+        moment_bins = np.stack([profile.read() for profile in profiles])
+        moment_totals = np.stack([profile.totals() for profile in profiles])
+        moment_counts = [profile.counts() for profile in profiles]
+        volume = profiles[0].volumes(args.moments_density) if args.moments_density is not None else None
+        for profile in profiles:
+            profile.close()
     if tracker is not None:
         history, lost, loss_counts = tracker.history(), tracker.read(), tracker.counts()
         tracker.close()
@@ -134,6 +159,21 @@ def main():
             path = args.output + "_loss_bins.nc"
             write_loss_bins(path, lost, tracker.redges, tracker.zedges, tracker.gedges, tracker.limit, tracker.psi0, tracker.span,
                             kind, **history, **loss_counts)
+            print("wrote %s" % path)
+    if profiles:
+        print("moments on %d surfaces of %s (normalised units%s):" % (args.moments, kind, ", confined particles" if tracker is not None else ""))
+        for step, total, count in zip(steps, moment_totals, moment_counts):
+            print("  step %6d: total current %.9e, total energy %.9e, %d outside, %d skipped"
+                  % (step, total[MOMENTS.index("current")], total[MOMENTS.index("energy")], count["outside"], count["skipped"]))
+        if args.output:
+            path = args.output + "_moment_bins.nc"
+            extra = {}
+            if volume is not None:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    extra = dict(volume=volume, sub=args.moments_density,
+                                 density=np.where(volume[None, :, None] == 0.0, np.nan, moment_bins/volume[None, :, None]))
+            write_moment_bins(path, moment_bins, medges, psi0, span, kind, totals=moment_totals, steps=steps,
+                              **{name: [count[name] for count in moment_counts] for name in ("samples", "outside", "skipped")}, **extra)
             print("wrote %s" % path)
     if args.output:
         path = args.output + "_phase_bins.nc"

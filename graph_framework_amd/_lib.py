@@ -138,6 +138,17 @@ SYMBOLS = [
     ("gfhip_confine_destroy", None, [_P]),
     ("gfhip_confine_check_host", _I, [_P, ctypes.c_double, _P, _S, _P, _S, _P, _S, _P, _I, _S, _U32, _P, _P, _P, _P,
                                       ctypes.POINTER(_U64), _P, _P]),
+    ("gfhip_moments_create", _P, [_P, _P, _P, _P, _S]),
+    ("gfhip_moments_add", _I, [_P, _P, _U64, _I, _S]),
+    ("gfhip_moments_values", _I, [_P, _P, _U64, _U64, _S]),
+    ("gfhip_moments_counts", _I, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("gfhip_moments_state", _I, [_P, _P]),
+    ("gfhip_moments_merge", _I, [_P, _P, _S, _S, _U64, _U64, _U64]),
+    ("gfhip_moments_read", _I, [_P, ctypes.c_double, _P]),
+    ("gfhip_moments_info", _I, [_P, _P]),
+    ("gfhip_moments_destroy", None, [_P]),
+    ("gfhip_moments_values_host", _I, [_P, _P, _P, _I, _S, _P, _P]),
+    ("gfhip_moments_add_host", _I, [_P, _P, _P, _S, _P, _I, _S, _P, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 

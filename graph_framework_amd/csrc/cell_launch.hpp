@@ -1,6 +1,7 @@
 //------------------------------------------------------------------------------
 ///  @file cell_launch.hpp
-///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip, flux_spectrum.hip, phase_bins.hip and confinement.hip.
+///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip, flux_spectrum.hip, phase_bins.hip, moment_bins.hip and
+///  confinement.hip.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_CELL_LAUNCH_HPP
 #define GFHIP_CELL_LAUNCH_HPP
@@ -78,6 +79,18 @@ void launch_phase_deposit(const void *const *columns, const bool is_f32, const s
 void launch_phase_coordinates(const void *const *columns, const bool is_f32, const size_t count, const flux::map &m,
                               const flux::field &f, const double *packed, const double *fpol, double *label, double *pitch,
                               hipStream_t stream);
+
+//  moment_bins.hip.  columns: as launch_phase_deposit's; edges: the ns + 1 of the label, sscale = ns/(last edge - first
+//  edge); the cell of (is, k) is is*4 + k, k = density, current, energy, radiation.  values: [particle][4].
+hipError_t moments_prepare();
+void launch_moment_deposit(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
+                           const flux::map &m, const flux::field &f, const double *packed, const double *fpol,
+                           const double *edges, const size_t ns, const double sscale, const bool is_private,
+                           const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
+                           void *state, unsigned long long *counters, hipStream_t stream);
+void launch_moment_values(const void *const *columns, const bool is_f32, const size_t count, const flux::map &m,
+                          const flux::field &f, const double *packed, const double *fpol, double *label, double *values,
+                          hipStream_t stream);
 
 //  confinement.hip.  columns: as launch_phase_deposit's, of which x, y, z, gamma and the weight are read; alive: the
 //  tracker's own column of the same type; edges: the n[0] + 1 of R, the n[1] + 1 of z, the n[2] + 1 of gamma; the cell of

@@ -254,6 +254,62 @@ GFHIP_HD double pitch_of(const double x, const double y, const double r, const d
     return canonical(xi);
 }
 
+//  The moments of a particle (x, y, z, ux, uy, uz, gamma), for moment_bins.hip: m = {1, v_par/c, gamma - 1, |B|^2 u_perp^2},
+//  the particle's share of the density, the parallel current, the kinetic energy (in m c^2) and the synchrotron power (up
+//  to constants), in the push's normalised units.  r, gr, gz and fpol as pitch_of takes them; every line one operation:
+//
+//      upar = cosine                  (u.B)/|B|, the value pitch_of divides by p
+//      vpar = upar/gamma              kin = gamma - 1.0
+//      uu   = (ux*ux + uy*uy) + uz*uz                 upup = upar*upar
+//      perp = uu - upup;   if (perp < 0) perp = 0     (a comparison: a NaN stays one; u along B cancels to a few ulp of uu)
+//      bsum = (gz*gz + f*f) + gr*gr                   rr = r*r          bsq = bsum/rr          (|B|^2)
+//      rad  = perp*bsq
+//
+//  u = 0 gives upar = 0 and rad = 0; gamma = 0 gives vpar = 0/0.  The four leave as canonical().
+GFHIP_HD void moments_of(const double x, const double y, const double r, const double ux, const double uy, const double uz,
+                         const double gamma, const double gr, const double gz, const double fpol, double *m) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double upar = cosine_of(x, y, r, ux, uy, uz, gr, gz, fpol);
+    const double vpar = upar/gamma;
+    const double kin = gamma - 1.0;
+    const double uxux = ux*ux;
+    const double uyuy = uy*uy;
+    const double uzuz = uz*uz;
+    const double uu = (uxux + uyuy) + uzuz;
+    const double upup = upar*upar;
+    double perp = uu - upup;
+    if (perp < 0.0) perp = 0.0;
+    const double gzgz = gz*gz;
+    const double ff = fpol*fpol;
+    const double grgr = gr*gr;
+    const double bsum = (gzgz + ff) + grgr;
+    const double rr = r*r;
+    const double bsq = bsum/rr;
+    const double rad = perp*bsq;
+    m[0] = 1.0;
+    m[1] = canonical(vpar);
+    m[2] = canonical(kin);
+    m[3] = canonical(rad);
+}
+
+//  What a particle of weight w deposits: v[0] = w, v[k] = w*m[k].
+GFHIP_HD void weighted_moments(const double w, const double *m, double *v) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    v[0] = w;
+    v[1] = w*m[1];
+    v[2] = w*m[2];
+    v[3] = w*m[3];
+}
+
+//  Whether a particle deposits at all: all four values finite, so that the four moments are sums over the same particles.
+GFHIP_HD bool moments_finite(const double *v) {
+    return superacc::is_finite(v[0]) && superacc::is_finite(v[1]) && superacc::is_finite(v[2]) && superacc::is_finite(v[3]);
+}
+
 //  The quadrature of the flux volumes (include/gf_hip.h): every table cell cut into sub x sub sub-cells, point
 //  (gr, gz) at the centre of sub-cell gr of numr*sub along R and gz of numz*sub along z, weighted with R times the
 //  sub-cell's area.  As above every line is one IEEE fp64 operation:

@@ -38,6 +38,7 @@
 #include "converge_state.hpp"
 #include "flux_label.hpp"
 #include "hand_over.hpp"
+#include "moments_host.hpp"
 #include "ray_batches.hpp"
 #include "superacc.hpp"
 
@@ -143,6 +144,7 @@ struct gfhip_context {
     std::vector<std::unique_ptr<gfhip_spectrum>> spectra;      // spectra (gfhip_spectrum_create), until gfhip_spectrum_destroy
     std::vector<std::unique_ptr<gfhip_phase>> phases;          // distributions (gfhip_phase_create), until gfhip_phase_destroy
     std::vector<std::unique_ptr<gfhip_confine>> confines;      // trackers (gfhip_confine_create), until gfhip_confine_destroy
+    std::vector<std::unique_ptr<gfhip_moments>> moments;       // moment profiles (gfhip_moments_create), until gfhip_moments_destroy
     std::string error;
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
@@ -286,6 +288,15 @@ struct gfhip_confine : flux_cells {
     std::vector<uint32_t> steps;                       // the checks made
     bool exit_ready = false;                           // the exit buffers of `exit_keys` hold NaN for every confined particle
     uint64_t exit_keys[2] = {0, 0};
+};
+
+//  The moments of particles per flux surface (moment_bins.hip): cell is*4 + k, k = density, current, energy, radiation;
+//  the edges of the label; fpol as [interval][4].
+struct gfhip_moments : flux_cells {
+    gfhip::flux::field field = {};
+    size_t ns = 0;
+    double sscale = 0.0;
+    device_ptr<double> fpol;
 };
 
 #define GFHIP_TRY(ctx, call, what) do { if ((ctx)->check((call), (what))) return 1; } while (0)
@@ -2396,6 +2407,182 @@ extern "C" int gfhip_phase_coordinates_host(const gfhip_flux_map *map, const gfh
             v[k] = is_f32 ? static_cast<double> (static_cast<const float *> (columns[k])[s]) : static_cast<const double *> (columns[k])[s];
         }
         phase_point(m, f, map, field, v[0], v[1], v[2], v[3], v[4], v[5], label[s], pitch[s]);
+    }
+    return 0;
+}
+
+//  Moment profiles (moment_bins.hip, flux_label.hpp): four cells per flux surface.  The surfaces are an axis of a
+//  distribution, 1 to 4096 (their edges are staged in LDS on both paths), so the 2^20 cells are never reached by an
+//  accepted axis; the check stands first for callers that ask for more.
+static const size_t moment_count = gfhip::moments::count;
+
+//  The label axis checked, or why it is refused.
+static const char *moments_axis_of(const double *sedges, const size_t ns) {
+    if (ns > phase_cell_limit/moment_count) return "a moment profile has at most 2^20 cells (four per surface, 536 B each)";
+    if (ns < 1 || ns > flux_cell_limit) return "a moment profile has 1 to 4096 surfaces (at least two edges)";
+    if (!edges_increase(sedges, ns)) return "the edges of a moment profile must be finite and strictly increasing";
+    return nullptr;
+}
+
+extern "C" gfhip_moments *gfhip_moments_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                               const double *sedges, size_t ns) {
+    if (!ctx) return nullptr;
+    if (!map || !field || !sedges) {
+        ctx->fail("a moment profile needs a map, a field and the label edges");
+        return nullptr;
+    }
+    if (const char *refused = moments_axis_of(sedges, ns)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    std::unique_ptr<gfhip_moments> p(new gfhip_moments);
+    if (const char *refused = phase_field_of(field, p->field)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    p->ns = ns;
+    p->sscale = static_cast<double> (ns)/(sedges[ns] - sedges[0]);
+    std::vector<double> lines;
+    if (!fpol_lines(field, lines)) {
+        ctx->fail("a moment profile's fpol tables do not fit the host's memory");
+        return nullptr;
+    }
+    if (p->create(ctx, map, ns*moment_count, std::vector<double> (sedges, sedges + ns + 1), gfhip::moments_prepare) ||
+        ctx->check(allocate(p->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
+        ctx->check(hipMemcpy(p->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
+        return nullptr;
+    }
+    ctx->moments.push_back(std::move(p));
+    return ctx->moments.back().get();
+}
+
+extern "C" void gfhip_moments_destroy(gfhip_moments *p) {
+    destroy_in(&gfhip_context::moments, p);
+}
+
+extern "C" int gfhip_moments_add(gfhip_moments *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count) {
+    if (!p) return 1;
+    if (!keys) return p->ctx->fail("gfhip_moments_add needs its 7 keys");
+    if (count == 0) return p->ctx->fail("a moment profile takes at least one particle");
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
+    const void *columns[8] = {};
+    bool is_f32 = false;
+    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32, "a moment profile")) return 1;
+    return p->add(count, [&](const size_t first, const size_t piece) {
+        gfhip::launch_moment_deposit(columns, is_f32, first, piece, p->map, p->field, p->packed.get(), p->fpol.get(),
+                                     p->edges.get(), p->ns, p->sscale, p->is_private, p->block, p->max_workgroups, p->lds_bytes,
+                                     p->state.get(), p->counters.get(), p->ctx->stream);
+    });
+}
+
+extern "C" int gfhip_moments_values(gfhip_moments *p, const uint64_t keys[7], uint64_t label_key, uint64_t values_key, size_t count) {
+    if (!p) return 1;
+    gfhip_context *ctx = p->ctx;
+    if (!keys) return ctx->fail("gfhip_moments_values needs its 7 keys");
+    if (count == 0) return ctx->fail("a moment profile takes at least one particle");
+    if (count > std::numeric_limits<size_t>::max()/moment_count) return ctx->fail("a moment profile's values buffer is shorter than 4 x the particle count");
+    const void *columns[8] = {};
+    bool is_f32 = false;
+    if (particle_columns(ctx, keys, 7, count, columns, is_f32, "a moment profile")) return 1;
+    double *label = nullptr, *values = nullptr;
+    if (fp64_columns(ctx, "a moment profile's label", {label_key}, count, &label) ||
+        fp64_columns(ctx, "a moment profile's values (4 per particle)", {values_key}, count*moment_count, &values)) {
+        return 1;
+    }
+    if (enter(ctx)) return 1;
+    gfhip::launch_moment_values(columns, is_f32, count, p->map, p->field, p->packed.get(), p->fpol.get(), label, values, ctx->stream);
+    GFHIP_TRY(ctx, hipGetLastError(), "moment values launch");
+    return 0;
+}
+
+extern "C" int gfhip_moments_counts(gfhip_moments *p, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
+    return p ? p->counts(samples, outside, skipped) : 1;
+}
+
+extern "C" int gfhip_moments_state(gfhip_moments *p, int64_t *limbs) {
+    if (!p) return 1;
+    if (!limbs) return p->ctx->fail("gfhip_moments_state needs a destination");
+    return p->state_to(limbs);
+}
+
+extern "C" int gfhip_moments_merge(gfhip_moments *p, const int64_t *limbs, size_t ns, size_t nm, uint64_t samples,
+                                   uint64_t outside, uint64_t skipped) {
+    if (!p) return 1;
+    if (!limbs) return p->ctx->fail("gfhip_moments_merge needs a state");
+    if (ns != p->ns || nm != moment_count) return p->ctx->fail("merge: a moment profile of another shape");
+    return p->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_moments_read(gfhip_moments *p, double divisor, double *values) {
+    if (!p) return 1;
+    if (!values) return p->ctx->fail("gfhip_moments_read needs a destination");
+    return p->read(divisor, values);
+}
+
+//  Not through enter(): as gfhip_flux_info.
+extern "C" int gfhip_moments_info(gfhip_moments *p, struct gfhip_flux_info *info) {
+    if (!p) return 1;
+    if (!info) return p->ctx->fail("gfhip_moments_info needs a destination");
+    p->info_to(info);
+    return 0;
+}
+
+//  The map, the field and the tables of a host call, or why they are refused.
+static const char *moments_host_of(const gfhip_flux_map *map, const gfhip_spectrum_field *field, gfhip::flux::map &m,
+                                   gfhip::flux::field &f, gfhip::moments::host_tables &t) {
+    if (const char *refused = flux_map_of(map, m)) return refused;
+    if (const char *refused = phase_field_of(field, f)) return refused;
+    t.coefficients = map->coefficients;
+    t.table = static_cast<size_t> (map->numr*map->numz);
+    for (size_t k = 0; k < 4; k++) t.fpol[k] = field->fpol[k];
+    return nullptr;
+}
+
+//  Host side, no device: flux_label.hpp on the caller's 16 + 4 tables (moments_host.hpp).
+extern "C" int gfhip_moments_values_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const void *const columns[7],
+                                         int is_f32, size_t count, double *label, double *values) {
+    bool complete = map && field && columns && ((label && values) || !count);
+    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
+    if (!complete) {
+        creation_error = "gfhip_moments_values_host needs a map, a field, seven columns and two destinations";
+        return 1;
+    }
+    gfhip::flux::map m;
+    gfhip::flux::field f;
+    gfhip::moments::host_tables t;
+    if (const char *refused = moments_host_of(map, field, m, f, t)) {
+        creation_error = refused;
+        return 1;
+    }
+    if (is_f32) {
+        gfhip::moments::values_host<float> (m, f, t, columns, count, label, values);
+    } else {
+        gfhip::moments::values_host<double> (m, f, t, columns, count, label, values);
+    }
+    return 0;
+}
+
+extern "C" int gfhip_moments_add_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *sedges, size_t ns,
+                                      const void *const columns[8], int is_f32, size_t count, int64_t *limbs, uint64_t counters[3]) {
+    bool complete = map && field && sedges && columns && limbs && counters;
+    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
+    if (!complete) {
+        creation_error = "gfhip_moments_add_host needs a map, a field, the label edges, seven columns, limbs and counters";
+        return 1;
+    }
+    gfhip::flux::map m;
+    gfhip::flux::field f;
+    gfhip::moments::host_tables t;
+    const char *refused = moments_axis_of(sedges, ns);
+    if (!refused) refused = moments_host_of(map, field, m, f, t);
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    if (is_f32) {
+        gfhip::moments::add_host<float> (m, f, t, sedges, ns, columns, count, limbs, counters);
+    } else {
+        gfhip::moments::add_host<double> (m, f, t, sedges, ns, columns, count, limbs, counters);
     }
     return 0;
 }

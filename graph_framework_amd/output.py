@@ -508,6 +508,57 @@ def write_phase_bins(path, bins, sbins, pbins, gbins, psi0, span, label="s", ste
     file.close()
 
 
+def write_moment_bins(path, bins, sbins, psi0, span, label="s", totals=None, steps=None, samples=None, outside=None, skipped=None,
+                      volume=None, density=None, sub=None, moments=("density", "current", "energy", "radiation")):
+    """moment_bins.nc, the snapshots of a push's moments per flux surface (moments.py), laid out as phase_bins.nc:
+    dimensions time, ns, nsp, nm; f8 variables bins(time, ns, nm), the sums per surface and moment, totals(time, nm), their
+    exact sums over the surfaces (bins summed when not given), sbins(nsp), the edges in the label; steps(time), the push's
+    step count at every snapshot, and samples(time), outside(time), skipped(time), what became of its particles (f8, as
+    every variable; zeros when not given); the moments' names (comma separated), their units ("normalised": the push's,
+    no physical constants), psi0 and span (f8) and the label kind as global attributes.  With `volume` (ns) and `density`
+    (time, ns, nm) (both or neither) also those variables, the cells' volumes in m^3 and bins/volume, and the quadrature's
+    sub as an integer attribute.  A single (ns, nm) array is one snapshot."""
+    if (volume is None) != (density is None):
+        raise ValueError("volume and density go together")
+    if volume is not None and sub is None:
+        raise ValueError("volume and density need the sub they were computed with")
+    bins = np.asarray(bins)
+    if bins.ndim == 2:
+        bins = bins[None]
+    if bins.ndim != 3 or bins.shape[2] != len(moments):
+        raise ValueError("a moment profile's bins are (time, ns, %d)" % len(moments))
+    sbins = np.asarray(sbins, dtype=np.float64).reshape(-1)
+    if sbins.size != bins.shape[1] + 1:
+        raise ValueError("bins of %d surfaces do not lie on %d edges" % (bins.shape[1], sbins.size))
+    totals = bins.sum(axis=1) if totals is None else np.asarray(totals, dtype=np.float64).reshape(-1, len(moments))
+    if totals.shape[0] != bins.shape[0]:
+        raise ValueError("totals need one row per snapshot")
+    if density is not None:
+        density = np.asarray(density, dtype=np.float64)
+        density = density[None] if density.ndim == 2 else density
+        if density.shape != bins.shape or np.size(volume) != bins.shape[1]:
+            raise ValueError("density has the bins' shape and volume one entry per surface")
+    file = BinsFile(path)
+    for name, length in (("time", bins.shape[0]), ("ns", bins.shape[1]), ("nsp", bins.shape[1] + 1), ("nm", bins.shape[2])):
+        file.create_dimension(name, length)
+    file.write_variable("bins", bins, ("time", "ns", "nm"))
+    file.write_variable("totals", totals, ("time", "nm"))
+    file.write_variable("sbins", sbins, ("nsp",))
+    for name, values in (("steps", steps), ("samples", samples), ("outside", outside), ("skipped", skipped)):
+        values = np.zeros(bins.shape[0]) if values is None else np.asarray(values, dtype=np.float64).reshape(-1)
+        file.write_variable(name, values, ("time",))
+    if volume is not None:
+        file.write_variable("volume", np.asarray(volume, dtype=np.float64).reshape(-1), ("ns",))
+        file.write_variable("density", density, ("time", "ns", "nm"))
+        file.int64_attribute("sub", sub)
+    file.text_attribute("moments", ",".join(moments))
+    file.text_attribute("units", "normalised")
+    file.float64_attribute("psi0", psi0)
+    file.float64_attribute("span", span)
+    file.text_attribute("label", label)
+    file.close()
+
+
 def write_loss_bins(path, bins, rbins, zbins, gbins, limit, psi0, span, label="s", steps=None, newly_lost=None, confined=None,
                     samples=0, outside=0, skipped=0):
     """loss_bins.nc, the losses of a push (confinement.py): dimensions nr, nrp, nz, nzp, ng, ngp, check; f8 variables

@@ -621,6 +621,65 @@ int gfhip_confine_check_host(const struct gfhip_flux_map *map, double limit, con
                              int is_f32, size_t count, uint32_t step, uint32_t *lost_step, void *alive, double *exit_r,
                              double *exit_z, uint64_t *newly_lost, int64_t *limbs, uint64_t counters[3]);
 
+/* Moments of the particles of a push per flux surface: density, parallel current, kinetic energy and synchrotron-radiated
+ * power, exact sums (csrc/moment_bins.hip).  In the push's normalised units: no physical constants are applied.
+ *
+ * The seven columns are a distribution's; the label, R, gR, gZ and f are those above, in the same fixed fp64 arithmetic of
+ * csrc/flux_label.hpp (fp32 columns widened first), every line one IEEE fp64 operation, nothing fused:
+ *     upar = cosine                            (u.B)/|B|, the value xi is cosine/p of
+ *     vpar = upar/gamma;  kin = gamma - 1.0
+ *     uu = (ux*ux + uy*uy) + uz*uz;  upup = upar*upar
+ *     perp = uu - upup;  if (perp < 0) perp = 0          (a comparison: a NaN stays a NaN)
+ *     bsum = (gZ*gZ + f*f) + gR*gR;  rr = R*R;  bsq = bsum/rr          (|B|^2)
+ *     rad = perp*bsq
+ *     m = {1.0, vpar, kin, rad}                GFHIP_MOMENT_DENSITY, _CURRENT, _ENERGY, _RADIATION
+ *     v[0] = w;  v[k] = w*m[k], k = 1..3       w: the weight, an eighth column of the same type, or 1.0 without one
+ * A particle belongs to surface `is` iff sedges[is] <= label < sedges[is+1] and deposits v[k] into the exact cell
+ * (is, k), flat index is*4 + k; state shape (ns, 4, 67).  The counters count particles: `samples` one per particle,
+ * `outside` the label in no cell (off the map, NaN, off the edges), `skipped` inside with any of the four v[k] NaN or
+ * infinite; such a particle deposits none of the four, so the four moments are sums over the same particles.  u = 0 is
+ * not skipped (upar = 0, rad = 0); gamma = 0 is (0/0).
+ *
+ * gfhip_moments_create: as gfhip_phase_create with the label edges alone.  Refused: what gfhip_phase_create refuses for
+ *   the map, the field and the edges (1 to 4096 surfaces); ns*4 > 2^20.  Up to 256 cells (64 surfaces) every workgroup
+ *   sums its deposits in LDS, unless the map sets GFHIP_FLUX_NO_PRIVATE_SUMS; the state is the same bytes either way, and
+ *   for fp32 and fp64 columns of equal values.
+ * gfhip_moments_add: keys and weight as gfhip_phase_add's.  Asynchronous on the context's stream; launches of at most
+ *   2^30 particles, normalised by the rule of gfhip_flux_add (a cell takes one deposit per particle).  Refused before
+ *   any launch, the state unchanged: an unknown key, a complex or mixed type, count = 0, a buffer shorter than `count`.
+ * gfhip_moments_values: the label and the four m[k] (a NaN as the quiet NaN, all NaN off the map) of `count` particles
+ *   into the fp64 buffers label_key (count) and values_key (4*count, [particle][k]).  Refused as _add, and a
+ *   destination that is not fp64 or too short.
+ * gfhip_moments_counts / _state / _read / _info / _destroy: as the distribution's; _merge takes the incoming state's
+ *   (ns, nm) and refuses another shape, nm != 4 included.
+ * gfhip_moments_values_host, gfhip_moments_add_host: no device, no context; the same lines on the CPU from the caller's
+ *   tables and arrays (csrc/moments_host.hpp), the columns float when is_f32 is non-zero and double otherwise,
+ *   columns[7] NULL without weights.  add_host adds to `limbs` (ns*4*67, canonical on return) and `counters` (3).
+ *   Errors: gfhip_last_error(NULL). */
+#define GFHIP_MOMENTS 4
+#define GFHIP_MOMENT_DENSITY 0
+#define GFHIP_MOMENT_CURRENT 1
+#define GFHIP_MOMENT_ENERGY 2
+#define GFHIP_MOMENT_RADIATION 3
+typedef struct gfhip_moments gfhip_moments;
+
+gfhip_moments *gfhip_moments_create(gfhip_context *ctx, const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                                    const double *sedges, size_t ns);
+int gfhip_moments_add(gfhip_moments *moments, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count);
+int gfhip_moments_values(gfhip_moments *moments, const uint64_t keys[7], uint64_t label_key, uint64_t values_key, size_t count);
+int gfhip_moments_counts(gfhip_moments *moments, uint64_t *samples, uint64_t *outside, uint64_t *skipped);
+int gfhip_moments_state(gfhip_moments *moments, int64_t *limbs);
+int gfhip_moments_merge(gfhip_moments *moments, const int64_t *limbs, size_t ns, size_t nm, uint64_t samples, uint64_t outside,
+                        uint64_t skipped);
+int gfhip_moments_read(gfhip_moments *moments, double divisor, double *values);
+int gfhip_moments_info(gfhip_moments *moments, struct gfhip_flux_info *info);
+void gfhip_moments_destroy(gfhip_moments *moments);
+int gfhip_moments_values_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                              const void *const columns[7], int is_f32, size_t count, double *label, double *values);
+int gfhip_moments_add_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field, const double *sedges,
+                           size_t ns, const void *const columns[8], int is_f32, size_t count, int64_t *limbs,
+                           uint64_t counters[3]);
+
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
  * Non-zero for a NaN or an infinity among the values (gfhip_last_error(NULL)). */
