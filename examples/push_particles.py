@@ -9,11 +9,15 @@ only, the confined fraction is printed per snapshot, and the losses over R, z an
 With --moments NS every snapshot also gets the exact density, parallel current, kinetic energy and radiated power on NS
 flux surfaces of the label range (graph_framework_amd/moments.py), under the same weights; the total current and energy
 are printed per snapshot and the profiles go to <output>_moment_bins.nc, with --moments-density SUB also per volume.
+With --particle-batches G the distribution and the moments are kept per batch of particles (graph_framework_amd/batches.py):
+the totals are printed with their standard error, and the files also get stderr, batch_bins and batch_particles (the
+moments' file means_stderr as well, the error of the moments per unit of density).
 
     python examples/push_particles.py --particles 1000000 --steps 200 --every 50 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
     python examples/push_particles.py --particles 100000 --dtype f64 --label-bins 16 --label-range 0,0.4 --pitch-bins 8 --gamma-bins 8 --gamma-range 1,3 --flux-tables tests/golden/efit_tables.npz
     python examples/push_particles.py --particles 1000000 --loss-limit 0.06 --loss-bins 32,32,8 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
     python examples/push_particles.py --particles 1000000 --moments 32 --moments-density 8 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
+    python examples/push_particles.py --particles 1000000 --moments 32 --particle-batches 64 --loss-limit 0.06 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
 
 The start positions are spread around the axis and the start momenta in size and pitch, seeded.  The push conserves gamma
 in a static field: the largest change of the gamma marginal between the first and the last snapshot is printed, the first
@@ -54,6 +58,12 @@ def box(text):
     return rlo, rhi, zlo, zhi
 
 
+def stacked(per_snapshot):
+    """The snapshots' dictionaries of arrays as one dictionary of arrays with the time axis first."""
+    import numpy as np
+    return {name: np.stack([each[name] for each in per_snapshot]) for name in per_snapshot[0]}
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--particles", type=int, default=100000)
@@ -75,6 +85,8 @@ def main():
                         help="also bin density, current, energy and radiated power on NS surfaces of --label-range")
     parser.add_argument("--moments-density", type=int, default=None, metavar="SUB",
                         help="with --moments: the file also gets the surfaces' volumes (quadrature SUB) and the moments per volume")
+    parser.add_argument("--particle-batches", type=int, default=None, metavar="G",
+                        help="keep the distribution and the moments per batch of particles, 1 to 256: error bars")
     parser.add_argument("--flux-tables", required=True, help="an .npz with efit.nc's psi and fpol tables (tests/golden/efit_tables.npz)")
     parser.add_argument("--output", default=None, help="prefix of <output>_phase_bins.nc (default: no file)")
     parser.add_argument("--seed", type=int, default=0)
@@ -84,6 +96,8 @@ def main():
         parser.error("--every needs 1 <= every <= steps")
     if args.moments is not None and args.moments < 1 or args.moments is None and args.moments_density is not None:
         parser.error("--moments needs NS >= 1, and --moments-density needs --moments")
+    if args.particle_batches is not None and not 1 <= args.particle_batches <= 256:
+        parser.error("--particle-batches needs 1 <= G <= 256")
 
     import numpy as np
     from graph_framework_amd import korc
@@ -117,23 +131,40 @@ def main():
     while done + args.every <= args.steps:
         push.run(args.every)
         done += args.every
-        snapshot = PhaseDistribution(push.work.context, tables, sedges, pedges, gedges, sqrt_label=args.sqrt_label)
+        snapshot = PhaseDistribution(push.work.context, tables, sedges, pedges, gedges, sqrt_label=args.sqrt_label,
+                                     batches=args.particle_batches)
         if tracker is not None:
             push.track(tracker)                              # settles the particles that have left since the last snapshot
         push.bin(snapshot, weight=tracker.alive_key if tracker is not None else None)        # behind the steps on the push's stream; the particles stay put
         snapshots.append(snapshot)
         steps.append(done)
         if args.moments is not None:
-            profiles.append(FluxMoments(push.work.context, tables, medges, sqrt_label=args.sqrt_label))
+            profiles.append(FluxMoments(push.work.context, tables, medges, sqrt_label=args.sqrt_label, batches=args.particle_batches))
             push.bin(profiles[-1], weight=tracker.alive_key if tracker is not None else None)
-    bins = np.stack([snapshot.read() for snapshot in snapshots])
+    batched = args.particle_batches is not None
+    errors, moment_errors = {}, {}
+    if batched:
+        from graph_framework_amd.batches import standard_error_of
+        from graph_framework_amd.flux import marginal_bins
+        bins = np.stack([marginal_bins(snapshot) for snapshot in snapshots])
+        errors = stacked([snapshot.sum_error_variables(push.first_particle, args.particles) for snapshot in snapshots])
+    else:
+        bins = np.stack([snapshot.read() for snapshot in snapshots])
     counts = [snapshot.counts() for snapshot in snapshots]
     kind, psi0, span = snapshots[0].label_kind, snapshots[0].psi0, snapshots[0].span
     for snapshot in snapshots:
         snapshot.close()
     if profiles:
-        moment_bins = np.stack([profile.read() for profile in profiles])
+        moment_bins = np.stack([marginal_bins(profile) if batched else profile.read() for profile in profiles])
         moment_totals = np.stack([profile.totals() for profile in profiles])
+        if batched:
+            moment_errors = stacked([profile.sum_error_variables(push.first_particle, args.particles) for profile in profiles])
+            moment_errors["means_stderr"] = np.stack([profile.means_error() for profile in profiles])
+#  The totals' error: N times the standard error of the per-particle mean, from the batches' sums over the surfaces.
+            total_errors = np.stack([args.particles*standard_error_of(profile.read().sum(axis=1), total,
+                                                                      profile.batch_rays(push.first_particle, args.particles),
+                                                                      args.particles)[1]
+                                     for profile, total in zip(profiles, moment_totals)])
         moment_counts = [profile.counts() for profile in profiles]
         volume = profiles[0].volumes(args.moments_density) if args.moments_density is not None else None
         for profile in profiles:
@@ -162,9 +193,15 @@ def main():
             print("wrote %s" % path)
     if profiles:
         print("moments on %d surfaces of %s (normalised units%s):" % (args.moments, kind, ", confined particles" if tracker is not None else ""))
-        for step, total, count in zip(steps, moment_totals, moment_counts):
-            print("  step %6d: total current %.9e, total energy %.9e, %d outside, %d skipped"
-                  % (step, total[MOMENTS.index("current")], total[MOMENTS.index("energy")], count["outside"], count["skipped"]))
+        current, energy = MOMENTS.index("current"), MOMENTS.index("energy")
+        for at, (step, total, count) in enumerate(zip(steps, moment_totals, moment_counts)):
+            if batched:
+                print("  step %6d: total current %.9e +- %.3e, total energy %.9e +- %.3e, %d outside, %d skipped"
+                      % (step, total[current], total_errors[at][current], total[energy], total_errors[at][energy],
+                         count["outside"], count["skipped"]))
+            else:
+                print("  step %6d: total current %.9e, total energy %.9e, %d outside, %d skipped"
+                      % (step, total[current], total[energy], count["outside"], count["skipped"]))
         if args.output:
             path = args.output + "_moment_bins.nc"
             extra = {}
@@ -173,12 +210,13 @@ def main():
                     extra = dict(volume=volume, sub=args.moments_density,
                                  density=np.where(volume[None, :, None] == 0.0, np.nan, moment_bins/volume[None, :, None]))
             write_moment_bins(path, moment_bins, medges, psi0, span, kind, totals=moment_totals, steps=steps,
-                              **{name: [count[name] for count in moment_counts] for name in ("samples", "outside", "skipped")}, **extra)
+                              **{name: [count[name] for count in moment_counts] for name in ("samples", "outside", "skipped")}, **extra,
+                              **moment_errors)
             print("wrote %s" % path)
     if args.output:
         path = args.output + "_phase_bins.nc"
         write_phase_bins(path, bins, sedges, pedges, gedges, psi0, span, kind, steps=steps,
-                         **{name: [count[name] for count in counts] for name in ("samples", "outside", "skipped")})
+                         **{name: [count[name] for count in counts] for name in ("samples", "outside", "skipped")}, **errors)
         print("wrote %s" % path)
 
 

@@ -149,6 +149,14 @@ SYMBOLS = [
     ("gfhip_moments_destroy", None, [_P]),
     ("gfhip_moments_values_host", _I, [_P, _P, _P, _I, _S, _P, _P]),
     ("gfhip_moments_add_host", _I, [_P, _P, _P, _S, _P, _I, _S, _P, _P]),
+    ("gfhip_phase_create_batched", _P, [_P, _P, _P, _P, _S, _P, _S, _P, _S, _S]),
+    ("gfhip_phase_add_particles", _I, [_P, _P, _U64, _I, _S, _U64]),
+    ("gfhip_phase_merge_batches", _I, [_P, _P, _S, _S, _S, _S, _U64, _U64, _U64]),
+    ("gfhip_phase_add_particles_host", _I, [_P, _P, _P, _S, _P, _S, _P, _S, _S, _P, _I, _S, _U64, _P, _P]),
+    ("gfhip_moments_create_batched", _P, [_P, _P, _P, _P, _S, _S]),
+    ("gfhip_moments_add_particles", _I, [_P, _P, _U64, _I, _S, _U64]),
+    ("gfhip_moments_merge_batches", _I, [_P, _P, _S, _S, _S, _U64, _U64, _U64]),
+    ("gfhip_moments_add_particles_host", _I, [_P, _P, _P, _S, _S, _P, _I, _S, _U64, _P, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
 ]
 

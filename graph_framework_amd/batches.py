@@ -3,7 +3,10 @@
 A cell of a flux profile or a spectrum is a Monte-Carlo estimate, the mean over rays of what each ray left in it.  The
 rays are divided into G fixed batches, ray r (its index in the whole ensemble over all ranks and files) into batch
 (r >> 6) % G, and the same tally is kept per batch (flux.FluxProfile and spectrum.FluxSpectrum with batches=G); the
-spread of the batch means is the standard error of the whole.  No device, no library: integers and fp64 numpy.
+spread of the batch means is the standard error of the whole.  The particles of a push are batched by the same rule,
+particle p of the whole ensemble over all ranks and shards in place of the ray (distribution.PhaseDistribution and
+moments.FluxMoments with batches=G); ratio_error_of is the error of a ratio of two such tallies.  No device, no library:
+integers and fp64 numpy.
 """
 import numpy as np
 
@@ -58,6 +61,29 @@ def standard_error_of(batch_sums, total, rays, count):
         deviation = sums[occupied]/n - mean
         stderr = np.sqrt((n*deviation*deviation).sum(axis=0)/((used - 1)*float(count)))
     return mean, stderr, used
+
+
+def ratio_error_of(batch_sums_num, batch_sums_den):
+    """The delete-one-batch jackknife standard error of the ratio of two tallied sums, in fp64 from the batches' rounded
+    exact sums: batch_sums_num and batch_sums_den (G, ...), S1_g and S0_g.  Over the m batches with particles (those
+    where S1_g or S0_g is not zero), with S1 and S0 their sums:
+        R_(g) = (S1 - S1_g)/(S0 - S0_g);  Rbar = sum_g R_(g)/m;  se = sqrt((m - 1)/m sum_g (R_(g) - Rbar)^2)
+    NaN with fewer than two such batches or where a denominator S0 - S0_g is zero."""
+    num = np.asarray(batch_sums_num, dtype=np.float64)
+    den = np.asarray(batch_sums_den, dtype=np.float64)
+    if num.shape != den.shape or num.ndim < 1:
+        raise ValueError("numerator sums of shape %r, denominator sums of shape %r" % (num.shape, den.shape))
+    used = (num != 0.0) | (den != 0.0)
+    m = used.sum(axis=0).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        num, den = np.where(used, num, 0.0), np.where(used, den, 0.0)
+        rest = den.sum(axis=0) - den
+        replicate = np.where(used, (num.sum(axis=0) - num)/rest, 0.0)
+        mean = replicate.sum(axis=0)/m
+        deviation = np.where(used, replicate - mean, 0.0)
+        error = np.sqrt((m - 1.0)/m*(deviation*deviation).sum(axis=0))
+    broken = (m < 2.0) | (used & (rest == 0.0)).any(axis=0)
+    return np.where(broken, np.nan, error)
 
 
 def largest_relative_error(mean, stderr, threshold=0.01):

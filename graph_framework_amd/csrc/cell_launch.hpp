@@ -76,6 +76,14 @@ void launch_phase_deposit(const void *const *columns, const bool is_f32, const s
                           const double *edges, const size_t *n, const double *scale, const bool is_private,
                           const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
                           void *state, unsigned long long *counters, hipStream_t stream);
+//  The same with the particles' indices in the ensemble (ray_batches.hpp's rule): particle first + i of the columns is
+//  particle first_particle + i; state: [batch][is][ip][ig][limb]; the launch shape is that of the cells of ONE batch.
+void launch_phase_deposit_particles(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
+                                    const unsigned long long first_particle, const size_t batch_count, const flux::map &m,
+                                    const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                                    const size_t *n, const double *scale, const bool is_private, const unsigned int block,
+                                    const size_t max_workgroups, const size_t lds_bytes, void *state,
+                                    unsigned long long *counters, hipStream_t stream);
 void launch_phase_coordinates(const void *const *columns, const bool is_f32, const size_t count, const flux::map &m,
                               const flux::field &f, const double *packed, const double *fpol, double *label, double *pitch,
                               hipStream_t stream);
@@ -88,6 +96,13 @@ void launch_moment_deposit(const void *const *columns, const bool is_f32, const 
                            const double *edges, const size_t ns, const double sscale, const bool is_private,
                            const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
                            void *state, unsigned long long *counters, hipStream_t stream);
+//  The same per batch of particles: state [batch][surface][moment][limb].
+void launch_moment_deposit_particles(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
+                                     const unsigned long long first_particle, const size_t batch_count, const flux::map &m,
+                                     const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                                     const size_t ns, const double sscale, const bool is_private, const unsigned int block,
+                                     const size_t max_workgroups, const size_t lds_bytes, void *state,
+                                     unsigned long long *counters, hipStream_t stream);
 void launch_moment_values(const void *const *columns, const bool is_f32, const size_t count, const flux::map &m,
                           const flux::field &f, const double *packed, const double *fpol, double *label, double *values,
                           hipStream_t stream);

@@ -1,8 +1,9 @@
 //------------------------------------------------------------------------------
 ///  @file flux_sums.hpp
-///  @brief What the deposit kernels of flux_profile.hip, flux_spectrum.hip and phase_bins.hip share (device side): the
-///  label of a point from the repacked psi tables, a workgroup's sums, private in LDS or global, and the deposit of the
-///  batched variants, one batch of rays (ray_batches.hpp) at a time.
+///  @brief What the deposit kernels of flux_profile.hip, flux_spectrum.hip, phase_bins.hip and moment_bins.hip share
+///  (device side): the label of a point from the repacked psi tables, a workgroup's sums, private in LDS or global, and
+///  the deposit of the batched variants, one batch of rays or particles (ray_batches.hpp) at a time, with one value per
+///  sample or several.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_FLUX_SUMS_HPP
 #define GFHIP_FLUX_SUMS_HPP
@@ -134,6 +135,44 @@ __device__ __forceinline__ void deposit_batched(const workgroup_sums<PRIVATE> &s
                   },
                   [&](const unsigned int g) {
                       sums.drain(state + static_cast<size_t> (g)*static_cast<size_t> (cells)*superacc::limbs);
+                  });
+    deposit::flush(tally, counters);
+}
+
+//  deposit_batched for samples that deposit K values each, all of them or none (moment_bins.hip: a particle and its four
+//  moments).  The cells are `groups` x K, cell group*K + k; the walk, the slabs and the drains are deposit_batched's.
+//  sample(at, v, finite): the group of sample `at`, or -1, its K values, and whether all of them are finite.  The
+//  sample is counted once, then the whole wave makes K adds.  counters: samples, outside, skipped, per sample.
+template<bool PRIVATE, int K, typename SAMPLE>
+__device__ __forceinline__ void deposit_batched_many(const workgroup_sums<PRIVATE> &sums, const unsigned long long first_ray,
+                                                     const unsigned long long count, const unsigned int batch_count,
+                                                     const int groups, unsigned long long *__restrict__ state,
+                                                     unsigned long long *__restrict__ counters, SAMPLE sample) {
+    deposit::tallies tally;
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t slab_words = static_cast<size_t> (groups)*K*superacc::limbs;
+    batches::walk(first_ray, count, batch_count, gridDim.x, blockDim.x >> 6, blockIdx.x, wave,
+                  [&](const unsigned int g, const uint64_t chunk_ray) {
+                      uint64_t at;
+                      const bool present = batches::sample_of(first_ray, count, chunk_ray, lane, at);
+                      int group = -1;                  // outside, as in the lanes that hold no sample
+                      double v[K];
+#pragma unroll
+                      for (int k = 0; k < K; k++) v[k] = 0.0;
+                      bool finite = true;
+                      if (present) group = sample(at, v, finite);
+//  Decided once per sample: inside, and all K finite or none deposited.
+                      const deposit::contribution whole = {group >= 0, finite, 0u, 0, 0, 0};
+                      deposit::count(tally, present, whole);
+                      const bool deposits = whole.inside && whole.finite;
+                      const unsigned int slab = PRIVATE ? 0u : g*static_cast<unsigned int> (groups);
+                      const unsigned int first = (slab + static_cast<unsigned int> (group))*K;
+#pragma unroll
+                      for (int k = 0; k < K; k++) sums.add(state, deposit::contribution_of(deposits, first + k, v[k]));
+                  },
+                  [&](const unsigned int g) {
+                      sums.drain(state + static_cast<size_t> (g)*slab_words);
                   });
     deposit::flush(tally, counters);
 }

@@ -39,6 +39,7 @@
 #include "flux_label.hpp"
 #include "hand_over.hpp"
 #include "moments_host.hpp"
+#include "phase_host.hpp"
 #include "ray_batches.hpp"
 #include "superacc.hpp"
 
@@ -249,6 +250,7 @@ struct flux_cells : exact_cells {
                hipError_t (*prepare)(), size_t batch_count = 0);
     void info_to(struct gfhip_flux_info *info) const;
     const char *rays_refused(uint64_t first_ray, size_t count) const;
+    const char *particles_refused(uint64_t first_particle, size_t count) const;
 };
 
 //  A flux-surface profile.
@@ -1844,6 +1846,13 @@ const char *flux_cells::rays_refused(const uint64_t first_ray, const size_t coun
     return nullptr;
 }
 
+//  The same for an add with a particle index (distributions and moment profiles).
+const char *flux_cells::particles_refused(const uint64_t first_particle, const size_t count) const {
+    if (!batches) return "only a batched object (gfhip_phase_create_batched, gfhip_moments_create_batched) takes particles with their index";
+    if (first_particle + static_cast<uint64_t> (count) < first_particle) return "first_particle + count overflows 64 bits";
+    return nullptr;
+}
+
 void flux_cells::info_to(struct gfhip_flux_info *info) const {
     info->private_sums = is_private ? 1u : 0u;
     info->workgroup_size = block;
@@ -2250,10 +2259,10 @@ static void phase_point(const gfhip::flux::map &m, const gfhip::flux::field &f, 
     pitch = gfhip::flux::pitch_of(x, y, gfhip::flux::radius_of(x, y), ux, uy, uz, gr, gz, gfhip::flux::fpol_of(cubic, tp));
 }
 
-extern "C" gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                           const double *sedges, size_t ns, const double *pedges, size_t np,
-                                           const double *gedges, size_t ng) {
-    if (!ctx) return nullptr;
+//  batch_count: 0 for gfhip_phase_create.
+static gfhip_phase *phase_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                 const double *sedges, size_t ns, const double *pedges, size_t np,
+                                 const double *gedges, size_t ng, const size_t batch_count, const bool batched) {
     if (!map || !field || !sedges || !pedges || !gedges) {
         ctx->fail("a distribution needs a map, a field and three edge arrays");
         return nullptr;
@@ -2278,6 +2287,10 @@ extern "C" gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const gfhip_flux_
         ctx->fail("a distribution has at most 2^20 cells (536 B each)");
         return nullptr;
     }
+    if (const char *refused = batched ? batches_refused(batch_count, cells) : nullptr) {
+        ctx->fail(refused);
+        return nullptr;
+    }
     std::unique_ptr<gfhip_phase> p(new gfhip_phase);
     if (const char *refused = phase_field_of(field, p->field)) {
         ctx->fail(refused);
@@ -2292,13 +2305,25 @@ extern "C" gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const gfhip_flux_
         ctx->fail("a distribution's fpol tables do not fit the host's memory");
         return nullptr;
     }
-    if (p->create(ctx, map, cells, edges, gfhip::phase_prepare) ||
+    if (p->create(ctx, map, cells, edges, gfhip::phase_prepare, batch_count) ||
         ctx->check(allocate(p->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
         ctx->check(hipMemcpy(p->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
         return nullptr;
     }
     ctx->phases.push_back(std::move(p));
     return ctx->phases.back().get();
+}
+
+extern "C" gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                           const double *sedges, size_t ns, const double *pedges, size_t np,
+                                           const double *gedges, size_t ng) {
+    return ctx ? phase_create(ctx, map, field, sedges, ns, pedges, np, gedges, ng, 0, false) : nullptr;
+}
+
+extern "C" gfhip_phase *gfhip_phase_create_batched(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                                   const double *sedges, size_t ns, const double *pedges, size_t np,
+                                                   const double *gedges, size_t ng, size_t batches) {
+    return ctx ? phase_create(ctx, map, field, sedges, ns, pedges, np, gedges, ng, batches, true) : nullptr;
 }
 
 extern "C" void gfhip_phase_destroy(gfhip_phase *p) {
@@ -2325,6 +2350,7 @@ static int particle_columns(gfhip_context *ctx, const uint64_t *keys, const size
 extern "C" int gfhip_phase_add(gfhip_phase *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count) {
     if (!p) return 1;
     if (!keys) return p->ctx->fail("gfhip_phase_add needs its 7 keys");
+    if (p->batches) return p->ctx->fail("a batched distribution takes its particles with their index: gfhip_phase_add_particles");
     const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
     const void *columns[8] = {};
     bool is_f32 = false;
@@ -2333,6 +2359,23 @@ extern "C" int gfhip_phase_add(gfhip_phase *p, const uint64_t keys[7], uint64_t 
         gfhip::launch_phase_deposit(columns, is_f32, first, piece, p->map, p->field, p->packed.get(), p->fpol.get(),
                                     p->edges.get(), p->n, p->scale, p->is_private, p->block, p->max_workgroups, p->lds_bytes,
                                     p->state.get(), p->counters.get(), p->ctx->stream);
+    });
+}
+
+extern "C" int gfhip_phase_add_particles(gfhip_phase *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count,
+                                         uint64_t first_particle) {
+    if (!p) return 1;
+    if (!keys) return p->ctx->fail("gfhip_phase_add_particles needs its 7 keys");
+    if (const char *refused = p->particles_refused(first_particle, count)) return p->ctx->fail(refused);
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
+    const void *columns[8] = {};
+    bool is_f32 = false;
+    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32)) return 1;
+    return p->add(count, [&](const size_t first, const size_t piece) {
+        gfhip::launch_phase_deposit_particles(columns, is_f32, first, piece, first_particle + first, p->batches, p->map, p->field,
+                                              p->packed.get(), p->fpol.get(), p->edges.get(), p->n, p->scale, p->is_private,
+                                              p->block, p->max_workgroups, p->lds_bytes, p->state.get(), p->counters.get(),
+                                              p->ctx->stream);
     });
 }
 
@@ -2366,7 +2409,17 @@ extern "C" int gfhip_phase_merge(gfhip_phase *p, const int64_t *limbs, size_t ns
                                  uint64_t outside, uint64_t skipped) {
     if (!p) return 1;
     if (!limbs) return p->ctx->fail("gfhip_phase_merge needs a state");
-    if (ns != p->n[0] || np != p->n[1] || ng != p->n[2]) return p->ctx->fail("merge: a distribution of another shape");
+    if (p->batches || ns != p->n[0] || np != p->n[1] || ng != p->n[2]) return p->ctx->fail("merge: a distribution of another shape");
+    return p->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_phase_merge_batches(gfhip_phase *p, const int64_t *limbs, size_t batches, size_t ns, size_t np, size_t ng,
+                                         uint64_t samples, uint64_t outside, uint64_t skipped) {
+    if (!p) return 1;
+    if (!limbs) return p->ctx->fail("gfhip_phase_merge_batches needs a state");
+    if (!p->batches || batches != p->batches || ns != p->n[0] || np != p->n[1] || ng != p->n[2]) {
+        return p->ctx->fail("merge: a distribution of another shape");
+    }
     return p->merge(limbs, samples, outside, skipped);
 }
 
@@ -2424,14 +2477,18 @@ static const char *moments_axis_of(const double *sedges, const size_t ns) {
     return nullptr;
 }
 
-extern "C" gfhip_moments *gfhip_moments_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                               const double *sedges, size_t ns) {
-    if (!ctx) return nullptr;
+//  batch_count: 0 for gfhip_moments_create.
+static gfhip_moments *moments_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                     const double *sedges, size_t ns, const size_t batch_count, const bool batched) {
     if (!map || !field || !sedges) {
         ctx->fail("a moment profile needs a map, a field and the label edges");
         return nullptr;
     }
     if (const char *refused = moments_axis_of(sedges, ns)) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    if (const char *refused = batched ? batches_refused(batch_count, ns*moment_count) : nullptr) {
         ctx->fail(refused);
         return nullptr;
     }
@@ -2447,13 +2504,24 @@ extern "C" gfhip_moments *gfhip_moments_create(gfhip_context *ctx, const gfhip_f
         ctx->fail("a moment profile's fpol tables do not fit the host's memory");
         return nullptr;
     }
-    if (p->create(ctx, map, ns*moment_count, std::vector<double> (sedges, sedges + ns + 1), gfhip::moments_prepare) ||
+    if (p->create(ctx, map, ns*moment_count, std::vector<double> (sedges, sedges + ns + 1), gfhip::moments_prepare, batch_count) ||
         ctx->check(allocate(p->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
         ctx->check(hipMemcpy(p->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
         return nullptr;
     }
     ctx->moments.push_back(std::move(p));
     return ctx->moments.back().get();
+}
+
+extern "C" gfhip_moments *gfhip_moments_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                               const double *sedges, size_t ns) {
+    return ctx ? moments_create(ctx, map, field, sedges, ns, 0, false) : nullptr;
+}
+
+extern "C" gfhip_moments *gfhip_moments_create_batched(gfhip_context *ctx, const gfhip_flux_map *map,
+                                                       const gfhip_spectrum_field *field, const double *sedges, size_t ns,
+                                                       size_t batches) {
+    return ctx ? moments_create(ctx, map, field, sedges, ns, batches, true) : nullptr;
 }
 
 extern "C" void gfhip_moments_destroy(gfhip_moments *p) {
@@ -2463,6 +2531,7 @@ extern "C" void gfhip_moments_destroy(gfhip_moments *p) {
 extern "C" int gfhip_moments_add(gfhip_moments *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count) {
     if (!p) return 1;
     if (!keys) return p->ctx->fail("gfhip_moments_add needs its 7 keys");
+    if (p->batches) return p->ctx->fail("a batched moment profile takes its particles with their index: gfhip_moments_add_particles");
     if (count == 0) return p->ctx->fail("a moment profile takes at least one particle");
     const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
     const void *columns[8] = {};
@@ -2472,6 +2541,24 @@ extern "C" int gfhip_moments_add(gfhip_moments *p, const uint64_t keys[7], uint6
         gfhip::launch_moment_deposit(columns, is_f32, first, piece, p->map, p->field, p->packed.get(), p->fpol.get(),
                                      p->edges.get(), p->ns, p->sscale, p->is_private, p->block, p->max_workgroups, p->lds_bytes,
                                      p->state.get(), p->counters.get(), p->ctx->stream);
+    });
+}
+
+extern "C" int gfhip_moments_add_particles(gfhip_moments *p, const uint64_t keys[7], uint64_t weight_key, int has_weight,
+                                           size_t count, uint64_t first_particle) {
+    if (!p) return 1;
+    if (!keys) return p->ctx->fail("gfhip_moments_add_particles needs its 7 keys");
+    if (const char *refused = p->particles_refused(first_particle, count)) return p->ctx->fail(refused);
+    if (count == 0) return p->ctx->fail("a moment profile takes at least one particle");
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
+    const void *columns[8] = {};
+    bool is_f32 = false;
+    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32, "a moment profile")) return 1;
+    return p->add(count, [&](const size_t first, const size_t piece) {
+        gfhip::launch_moment_deposit_particles(columns, is_f32, first, piece, first_particle + first, p->batches, p->map, p->field,
+                                               p->packed.get(), p->fpol.get(), p->edges.get(), p->ns, p->sscale, p->is_private,
+                                               p->block, p->max_workgroups, p->lds_bytes, p->state.get(), p->counters.get(),
+                                               p->ctx->stream);
     });
 }
 
@@ -2509,7 +2596,17 @@ extern "C" int gfhip_moments_merge(gfhip_moments *p, const int64_t *limbs, size_
                                    uint64_t outside, uint64_t skipped) {
     if (!p) return 1;
     if (!limbs) return p->ctx->fail("gfhip_moments_merge needs a state");
-    if (ns != p->ns || nm != moment_count) return p->ctx->fail("merge: a moment profile of another shape");
+    if (p->batches || ns != p->ns || nm != moment_count) return p->ctx->fail("merge: a moment profile of another shape");
+    return p->merge(limbs, samples, outside, skipped);
+}
+
+extern "C" int gfhip_moments_merge_batches(gfhip_moments *p, const int64_t *limbs, size_t batches, size_t ns, size_t nm,
+                                           uint64_t samples, uint64_t outside, uint64_t skipped) {
+    if (!p) return 1;
+    if (!limbs) return p->ctx->fail("gfhip_moments_merge_batches needs a state");
+    if (!p->batches || batches != p->batches || ns != p->ns || nm != moment_count) {
+        return p->ctx->fail("merge: a moment profile of another shape");
+    }
     return p->merge(limbs, samples, outside, skipped);
 }
 
@@ -2583,6 +2680,86 @@ extern "C" int gfhip_moments_add_host(const gfhip_flux_map *map, const gfhip_spe
         gfhip::moments::add_host<float> (m, f, t, sedges, ns, columns, count, limbs, counters);
     } else {
         gfhip::moments::add_host<double> (m, f, t, sedges, ns, columns, count, limbs, counters);
+    }
+    return 0;
+}
+
+//  The batches and the particle range of a host call, or why they are refused.
+static const char *host_batches_refused(const size_t batches, const uint64_t first_particle, const size_t count) {
+    if (batches < 1 || batches > gfhip::batches::max_batches) return "a batched object has 1 to 256 batches";
+    if (first_particle + static_cast<uint64_t> (count) < first_particle) return "first_particle + count overflows 64 bits";
+    return nullptr;
+}
+
+//  limbs: [batches][ns][4][67] (moments_host.hpp's add_particles_host).
+extern "C" int gfhip_moments_add_particles_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *sedges,
+                                                size_t ns, size_t batches, const void *const columns[8], int is_f32, size_t count,
+                                                uint64_t first_particle, int64_t *limbs, uint64_t counters[3]) {
+    bool complete = map && field && sedges && columns && limbs && counters;
+    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
+    if (!complete) {
+        creation_error = "gfhip_moments_add_particles_host needs a map, a field, the label edges, seven columns, limbs and counters";
+        return 1;
+    }
+    gfhip::flux::map m;
+    gfhip::flux::field f;
+    gfhip::moments::host_tables t;
+    const char *refused = moments_axis_of(sedges, ns);
+    if (!refused) refused = host_batches_refused(batches, first_particle, count);
+    if (!refused) refused = moments_host_of(map, field, m, f, t);
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    if (is_f32) {
+        gfhip::moments::add_particles_host<float> (m, f, t, sedges, ns, static_cast<unsigned int> (batches), first_particle, columns,
+                                                   count, limbs, counters);
+    } else {
+        gfhip::moments::add_particles_host<double> (m, f, t, sedges, ns, static_cast<unsigned int> (batches), first_particle,
+                                                    columns, count, limbs, counters);
+    }
+    return 0;
+}
+
+//  limbs: [batches][ns][np][ng][67] (phase_host.hpp's add_particles_host).
+extern "C" int gfhip_phase_add_particles_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *sedges,
+                                              size_t ns, const double *pedges, size_t np, const double *gedges, size_t ng,
+                                              size_t batches, const void *const columns[8], int is_f32, size_t count,
+                                              uint64_t first_particle, int64_t *limbs, uint64_t counters[3]) {
+    bool complete = map && field && sedges && pedges && gedges && columns && limbs && counters;
+    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
+    if (!complete) {
+        creation_error = "gfhip_phase_add_particles_host needs a map, a field, three edge arrays, seven columns, limbs and counters";
+        return 1;
+    }
+    const double *axes[3] = {sedges, pedges, gedges};
+    const size_t n[3] = {ns, np, ng};
+    gfhip::flux::map m;
+    gfhip::flux::field f;
+    gfhip::moments::host_tables t;
+    const char *refused = nullptr;
+    size_t cells = 1;
+    for (int a = 0; !refused && a < 3; a++) {
+        if (n[a] < 1 || n[a] > flux_cell_limit) {
+            refused = "a distribution has 1 to 4096 cells per axis (at least two edges)";
+        } else if (!edges_increase(axes[a], n[a])) {
+            refused = "the edges of a distribution must be finite and strictly increasing";
+        }
+        cells *= n[a];
+    }
+    if (!refused && cells > phase_cell_limit) refused = "a distribution has at most 2^20 cells (536 B each)";
+    if (!refused) refused = host_batches_refused(batches, first_particle, count);
+    if (!refused) refused = moments_host_of(map, field, m, f, t);
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    if (is_f32) {
+        gfhip::phase::add_particles_host<float> (m, f, t, axes, n, static_cast<unsigned int> (batches), first_particle, columns,
+                                                 count, limbs, counters);
+    } else {
+        gfhip::phase::add_particles_host<double> (m, f, t, axes, n, static_cast<unsigned int> (batches), first_particle, columns,
+                                                  count, limbs, counters);
     }
     return 0;
 }

@@ -15,6 +15,10 @@
 ///  staged behind it; above that, or with the map's no-private flag, deposits go to the global state behind the wave
 ///  pre-sum (particles without a weight on one surface share the limbs of moment 0: three atomics per wave for it).
 ///  The state does not depend on the route, the launch shape, the order of the particles or their type.
+///
+///  moment_deposit_particles_kernel keeps the same sums per batch of particles (ray_batches.hpp, the particle's index in
+///  the ensemble in place of a ray's), state [batch][surface][moment][limb]: a workgroup works on one batch at a time, so
+///  the private grid is still ns*4 cells whatever the number of batches.
 //------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -111,6 +115,34 @@ moment_deposit_kernel(const moment_columns<T> in, const unsigned long long count
     deposit::flush(tally, counters);
 }
 
+//  moment_deposit_kernel with the particles' indices in the ensemble: sample i is particle first_particle + i, and the
+//  state is [batch][surface][moment][limb] (flux_sums.hpp's deposit_batched_many).  A workgroup holds the ns*4 cells of
+//  ONE batch of particles (ray_batches.hpp's rule, a particle in place of a ray) whatever the number of batches.
+template<bool PRIVATE, typename T>
+__global__ void __launch_bounds__(private_block)
+moment_deposit_particles_kernel(const moment_columns<T> in, const unsigned long long count, const unsigned long long first_particle,
+                                const unsigned int batch_count, const flux::map m, const flux::field f,
+                                const double *__restrict__ packed, const double *__restrict__ fpol,
+                                const double *__restrict__ edges, const int ns, const double sscale,
+                                unsigned long long *__restrict__ state, unsigned long long *__restrict__ counters) {
+    extern __shared__ unsigned long long shared[];
+    workgroup_sums<PRIVATE> sums;
+    sums.open(shared, edges, ns*moment_count, ns + 1);
+    const double *sedge = sums.staged;
+    deposit_batched_many<PRIVATE, moment_count> (sums, first_particle, count, batch_count, ns, state, counters,
+                                                 [&](const uint64_t at, double *v, bool &finite) {
+        const double w = in.weight ? static_cast<double> (in.weight[at]) : 1.0;
+        double moments[moment_count];
+        const double label = moments_at(m, f, packed, fpol, static_cast<double> (in.x[at]), static_cast<double> (in.y[at]),
+                                        static_cast<double> (in.z[at]), static_cast<double> (in.ux[at]),
+                                        static_cast<double> (in.uy[at]), static_cast<double> (in.uz[at]),
+                                        static_cast<double> (in.gamma[at]), moments);
+        flux::weighted_moments(w, moments, v);
+        finite = flux::moments_finite(v);
+        return deposit::find_cell(sedge, ns, sscale, label);
+    });
+}
+
 //  One lane per particle: its label and its four moments, values[at*4 + k], NaN outside the map.
 template<typename T>
 __global__ void __launch_bounds__(256)
@@ -131,7 +163,9 @@ moment_values_kernel(const moment_columns<T> in, const unsigned long long count,
 //  Dynamic LDS above 64 KiB has to be asked for: always the cap's size, as flux_prepare does.
 hipError_t moments_prepare() {
     for (const void *kernel : {reinterpret_cast<const void *> (&moment_deposit_kernel<true, float>),
-                               reinterpret_cast<const void *> (&moment_deposit_kernel<true, double>)}) {
+                               reinterpret_cast<const void *> (&moment_deposit_kernel<true, double>),
+                               reinterpret_cast<const void *> (&moment_deposit_particles_kernel<true, float>),
+                               reinterpret_cast<const void *> (&moment_deposit_particles_kernel<true, double>)}) {
         const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                       static_cast<int> (moment_cap_bytes));
         if (status != hipSuccess) return status;
@@ -166,6 +200,25 @@ void deposit_as(const void *const *columns, const size_t first, const size_t cou
     }
 }
 
+template<typename T>
+void deposit_particles_as(const void *const *columns, const size_t first, const size_t count, const unsigned long long first_particle,
+                          const size_t batch_count, const flux::map &m, const flux::field &f, const double *packed,
+                          const double *fpol, const double *edges, const size_t ns, const double sscale, const bool is_private,
+                          const unsigned int block, const size_t max_workgroups, const size_t lds_bytes, void *state,
+                          unsigned long long *counters, hipStream_t stream) {
+    const moment_columns<T> in = columns_from<T> (columns, first, columns[7] != nullptr);
+    const unsigned int grid = batched_grid_of(count, block, max_workgroups, batch_count);
+    if (is_private) {
+        hipLaunchKernelGGL((moment_deposit_particles_kernel<true, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), first_particle, static_cast<unsigned int> (batch_count), m, f,
+                           packed, fpol, edges, static_cast<int> (ns), sscale, static_cast<unsigned long long *> (state), counters);
+    } else {
+        hipLaunchKernelGGL((moment_deposit_particles_kernel<false, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), first_particle, static_cast<unsigned int> (batch_count), m, f,
+                           packed, fpol, edges, static_cast<int> (ns), sscale, static_cast<unsigned long long *> (state), counters);
+    }
+}
+
 }  // namespace
 
 void launch_moment_deposit(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
@@ -180,6 +233,22 @@ void launch_moment_deposit(const void *const *columns, const bool is_f32, const 
     } else {
         deposit_as<double> (columns, first, count, m, f, packed, fpol, edges, ns, sscale, is_private, block, max_workgroups,
                             lds_bytes, state, counters, stream);
+    }
+}
+
+void launch_moment_deposit_particles(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
+                                     const unsigned long long first_particle, const size_t batch_count, const flux::map &m,
+                                     const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                                     const size_t ns, const double sscale, const bool is_private, const unsigned int block,
+                                     const size_t max_workgroups, const size_t lds_bytes, void *state,
+                                     unsigned long long *counters, hipStream_t stream) {
+    if (count == 0) return;
+    if (is_f32) {
+        deposit_particles_as<float> (columns, first, count, first_particle, batch_count, m, f, packed, fpol, edges, ns, sscale,
+                                     is_private, block, max_workgroups, lds_bytes, state, counters, stream);
+    } else {
+        deposit_particles_as<double> (columns, first, count, first_particle, batch_count, m, f, packed, fpol, edges, ns, sscale,
+                                      is_private, block, max_workgroups, lds_bytes, state, counters, stream);
     }
 }
 

@@ -1,7 +1,7 @@
 //------------------------------------------------------------------------------
 ///  @file moments_host.hpp
 ///  @brief The moment deposit of moment_bins.hip on the CPU, particle by particle (gfhip_moments_values_host,
-///  gfhip_moments_add_host).
+///  gfhip_moments_add_host, and per batch of particles gfhip_moments_add_particles_host).
 ///
 ///  The same lines as the kernel's on the caller's arrays: the label and the four moments from flux_label.hpp on the 16
 ///  coefficient tables and the four fpol tables as the caller holds them ([k][table cell], [k][interval]), the surface by
@@ -18,6 +18,7 @@
 #include <limits>
 
 #include "flux_label.hpp"
+#include "ray_batches.hpp"
 #include "superacc.hpp"
 
 namespace gfhip {
@@ -99,6 +100,48 @@ void add_host(const flux::map &m, const flux::field &f, const host_tables &t, co
             pending = 1;
         }
         for (size_t k = 0; k < count; k++) superacc::deposit(limbs + (static_cast<size_t> (is)*count + k)*superacc::limbs, v[k]);
+    }
+    if (pending) normalise_all();
+    counters[0] += particles;
+    counters[1] += outside;
+    counters[2] += skipped;
+}
+
+//  add_host per batch of particles (ray_batches.hpp's rule, a particle's index in the ensemble in place of a ray's):
+//  particle s of the columns is particle first_particle + s.  limbs: [batch][ns*4 cells][67], slab g what add_host makes
+//  of batch g's particles alone; counters: samples, outside, skipped of all of them, per particle.
+template<typename T>
+void add_particles_host(const flux::map &m, const flux::field &f, const host_tables &t, const double *sedges, const size_t ns,
+                        const unsigned int batch_count, const uint64_t first_particle, const void *const *columns,
+                        const size_t particles, int64_t *limbs, uint64_t *counters) {
+    const T *const *in = reinterpret_cast<const T *const *> (columns);
+    const size_t cells = ns*count;
+    const auto normalise_all = [&]() {
+        for (size_t cell = 0; cell < batch_count*cells; cell++) superacc::normalise(limbs + cell*superacc::limbs);
+    };
+    uint64_t pending = 0, outside = 0, skipped = 0;
+    for (size_t s = 0; s < particles; s++) {
+        double moments[count], v[count];
+        const double label = host_point(m, f, t, static_cast<double> (in[0][s]), static_cast<double> (in[1][s]),
+                                        static_cast<double> (in[2][s]), static_cast<double> (in[3][s]),
+                                        static_cast<double> (in[4][s]), static_cast<double> (in[5][s]),
+                                        static_cast<double> (in[6][s]), moments);
+        const long long is = host_cell(sedges, ns, label);
+        if (is < 0) {
+            outside++;
+            continue;
+        }
+        flux::weighted_moments(in[7] ? static_cast<double> (in[7][s]) : 1.0, moments, v);
+        if (!flux::moments_finite(v)) {                // all four or none
+            skipped++;
+            continue;
+        }
+        if (++pending > superacc::deposits_per_normalise) {    // a cell takes at most one deposit per particle
+            normalise_all();
+            pending = 1;
+        }
+        int64_t *slab = limbs + batches::batch_of(first_particle + s, batch_count)*cells*superacc::limbs;
+        for (size_t k = 0; k < count; k++) superacc::deposit(slab + (static_cast<size_t> (is)*count + k)*superacc::limbs, v[k]);
     }
     if (pending) normalise_all();
     counters[0] += particles;

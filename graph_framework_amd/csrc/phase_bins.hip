@@ -14,6 +14,9 @@
 ///  behind it; above that, or with the map's no-private flag, deposits go to the global state behind the wave pre-sum
 ///  (particles without a weight that share a cell share the limbs too: three atomics per wave).  The state does not
 ///  depend on the route, the launch shape, the order of the particles or their type.
+///
+///  phase_deposit_particles_kernel keeps the same sums per batch of particles (ray_batches.hpp, the particle's index in
+///  the ensemble in place of a ray's), state [batch][is][ip][ig][limb], one batch at a time in a workgroup's LDS.
 //------------------------------------------------------------------------------
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,6 +107,33 @@ phase_deposit_kernel(const phase_columns<T> in, const unsigned long long count,
     deposit::flush(tally, counters);
 }
 
+//  phase_deposit_kernel with the particles' indices in the ensemble: sample i is particle first_particle + i, and the
+//  state is [batch][is][ip][ig][limb] (flux_sums.hpp's deposit_batched, a particle in place of a ray).
+template<bool PRIVATE, typename T>
+__global__ void __launch_bounds__(private_block)
+phase_deposit_particles_kernel(const phase_columns<T> in, const unsigned long long count, const unsigned long long first_particle,
+                               const unsigned int batch_count, const flux::map m, const flux::field f,
+                               const double *__restrict__ packed, const double *__restrict__ fpol,
+                               const double *__restrict__ edges, const int ns, const int np, const int ng,
+                               const double sscale, const double pscale, const double gscale,
+                               unsigned long long *__restrict__ state, unsigned long long *__restrict__ counters) {
+    extern __shared__ unsigned long long shared[];
+    workgroup_sums<PRIVATE> sums;
+    sums.open(shared, edges, ns*np*ng, ns + np + ng + 3);
+    const double *sedge = sums.staged, *pedge = sedge + ns + 1, *gedge = pedge + np + 1;
+    deposit_batched(sums, first_particle, count, batch_count, ns*np*ng, state, counters, [&](const uint64_t at, double &v) {
+        v = in.weight ? static_cast<double> (in.weight[at]) : 1.0;
+        double label;
+        const double xi = pitch_at(m, f, packed, fpol, static_cast<double> (in.x[at]), static_cast<double> (in.y[at]),
+                                   static_cast<double> (in.z[at]), static_cast<double> (in.ux[at]),
+                                   static_cast<double> (in.uy[at]), static_cast<double> (in.uz[at]), label);
+        const int is = deposit::find_cell(sedge, ns, sscale, label);
+        const int ip = deposit::find_cell(pedge, np, pscale, xi);
+        const int ig = deposit::find_cell(gedge, ng, gscale, static_cast<double> (in.gamma[at]));
+        return is >= 0 && ip >= 0 && ig >= 0 ? (is*np + ip)*ng + ig : -1;
+    });
+}
+
 //  One lane per particle: its label and its xi, NaN outside the map.
 template<typename T>
 __global__ void __launch_bounds__(256)
@@ -123,7 +153,9 @@ phase_coordinates_kernel(const phase_columns<T> in, const unsigned long long cou
 //  Dynamic LDS above 64 KiB has to be asked for: always the cap's size, as flux_prepare does.
 hipError_t phase_prepare() {
     for (const void *kernel : {reinterpret_cast<const void *> (&phase_deposit_kernel<true, float>),
-                               reinterpret_cast<const void *> (&phase_deposit_kernel<true, double>)}) {
+                               reinterpret_cast<const void *> (&phase_deposit_kernel<true, double>),
+                               reinterpret_cast<const void *> (&phase_deposit_particles_kernel<true, float>),
+                               reinterpret_cast<const void *> (&phase_deposit_particles_kernel<true, double>)}) {
         const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                       static_cast<int> (phase_cap_bytes));
         if (status != hipSuccess) return status;
@@ -160,6 +192,27 @@ void deposit_as(const void *const *columns, const size_t first, const size_t cou
     }
 }
 
+template<typename T>
+void deposit_particles_as(const void *const *columns, const size_t first, const size_t count, const unsigned long long first_particle,
+                          const size_t batch_count, const flux::map &m, const flux::field &f, const double *packed,
+                          const double *fpol, const double *edges, const size_t *n, const double *scale, const bool is_private,
+                          const unsigned int block, const size_t max_workgroups, const size_t lds_bytes, void *state,
+                          unsigned long long *counters, hipStream_t stream) {
+    const phase_columns<T> in = columns_from<T> (columns, first, columns[7] != nullptr);
+    const unsigned int grid = batched_grid_of(count, block, max_workgroups, batch_count);
+    if (is_private) {
+        hipLaunchKernelGGL((phase_deposit_particles_kernel<true, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), first_particle, static_cast<unsigned int> (batch_count), m, f,
+                           packed, fpol, edges, static_cast<int> (n[0]), static_cast<int> (n[1]), static_cast<int> (n[2]),
+                           scale[0], scale[1], scale[2], static_cast<unsigned long long *> (state), counters);
+    } else {
+        hipLaunchKernelGGL((phase_deposit_particles_kernel<false, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
+                           static_cast<unsigned long long> (count), first_particle, static_cast<unsigned int> (batch_count), m, f,
+                           packed, fpol, edges, static_cast<int> (n[0]), static_cast<int> (n[1]), static_cast<int> (n[2]),
+                           scale[0], scale[1], scale[2], static_cast<unsigned long long *> (state), counters);
+    }
+}
+
 }  // namespace
 
 void launch_phase_deposit(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
@@ -174,6 +227,22 @@ void launch_phase_deposit(const void *const *columns, const bool is_f32, const s
     } else {
         deposit_as<double> (columns, first, count, m, f, packed, fpol, edges, n, scale, is_private, block, max_workgroups,
                             lds_bytes, state, counters, stream);
+    }
+}
+
+void launch_phase_deposit_particles(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
+                                    const unsigned long long first_particle, const size_t batch_count, const flux::map &m,
+                                    const flux::field &f, const double *packed, const double *fpol, const double *edges,
+                                    const size_t *n, const double *scale, const bool is_private, const unsigned int block,
+                                    const size_t max_workgroups, const size_t lds_bytes, void *state,
+                                    unsigned long long *counters, hipStream_t stream) {
+    if (count == 0) return;
+    if (is_f32) {
+        deposit_particles_as<float> (columns, first, count, first_particle, batch_count, m, f, packed, fpol, edges, n, scale,
+                                     is_private, block, max_workgroups, lds_bytes, state, counters, stream);
+    } else {
+        deposit_particles_as<double> (columns, first, count, first_particle, batch_count, m, f, packed, fpol, edges, n, scale,
+                                      is_private, block, max_workgroups, lds_bytes, state, counters, stream);
     }
 }
 

@@ -18,7 +18,7 @@ import ctypes
 import numpy as np
 
 from .backend import GfHipError, key_of
-from .exact_cells import LIMBS, ExactCells
+from .exact_cells import LIMBS, RayBatches
 from .flux import FluxProfile, _Info, flux_map
 from .spectrum import _keys, spectrum_field
 
@@ -58,12 +58,45 @@ def coordinates_host(tables, columns, psi0=None, span=None, sqrt_label=False):
     return label, pitch
 
 
-class PhaseDistribution(ExactCells):
+def add_particles_host(tables, sedges, pedges, gedges, batches, columns, first, weight=None, limbs=None, counters=None,
+                       psi0=None, span=None, sqrt_label=False):
+    """The exact deposit of a PhaseDistribution with batches on the CPU (gfhip_phase_add_particles_host): particle i of
+    the columns is particle first + i of the ensemble.  (limbs (batches, ns, np, ng, 67) int64, counters (3,) uint64), the
+    bytes and numbers of state() and counts() after the same add_particles; given `limbs` and `counters`, added to in
+    place."""
+    from . import _lib
+    from .moments import _host_columns
+    lib = _lib.load()
+    given, keep = flux_map(tables, psi0, span, sqrt_label)
+    field, keep_field = spectrum_field(tables)
+    edges = [np.ascontiguousarray(e, dtype=np.float64).reshape(-1) for e in (sedges, pedges, gedges)]
+    if min(e.size for e in edges) < 2:
+        raise ValueError("a distribution needs at least two edges per axis")
+    shape = (int(batches),) + tuple(e.size - 1 for e in edges) + (LIMBS,)
+    if limbs is None:
+        limbs, counters = np.zeros(shape, dtype=np.int64), np.zeros(3, dtype=np.uint64)
+    for name, array, kind, want in (("limbs", limbs, np.int64, shape), ("counters", counters, np.uint64, (3,))):
+        if not isinstance(array, np.ndarray) or array.dtype != kind or array.shape != want or not array.flags["C_CONTIGUOUS"]:
+            raise ValueError("%s must be a contiguous %s array of shape %r: it is updated in place" % (name, np.dtype(kind).name, want))
+    columns, is_f32 = _host_columns(columns, weight)
+    pointers = (ctypes.c_void_p*8)(*[column.ctypes.data for column in columns])
+    axes = [value for e in edges for value in (e.ctypes.data, e.size - 1)]
+    if lib.gfhip_phase_add_particles_host(ctypes.byref(given), ctypes.byref(field), *axes, int(batches), pointers, int(is_f32),
+                                          columns[0].size, int(first), limbs.ctypes.data, counters.ctypes.data):
+        raise GfHipError(lib.gfhip_last_error(None).decode())
+    del keep, keep_field
+    return limbs, counters
+
+
+class PhaseDistribution(RayBatches):
     """A grid of exact sums over (label, xi, gamma) on a context's device (gfhip_phase_*, include/gf_hip.h); state() is
-    (ns, np, ng, 67)."""
+    (ns, np, ng, 67).  batches=G: the same sums per batch of particles (batches.py, the particle's index in the ensemble
+    in place of a ray's), state() (G, ns, np, ng, 67), fed with add_particles; total() is the plain distribution and
+    standard_error() the error bar of its cells."""
     prefix = "phase"
 
-    def __init__(self, context, tables, sedges, pedges, gedges, psi0=None, span=None, sqrt_label=False, private=True):
+    def __init__(self, context, tables, sedges, pedges, gedges, psi0=None, span=None, sqrt_label=False, private=True,
+                 batches=None):
         self.tables = tables
         self.sedges, self.pedges, self.gedges = (np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
                                                  for edges in (sedges, pedges, gedges))
@@ -74,15 +107,14 @@ class PhaseDistribution(ExactCells):
         given, keep = flux_map(tables, psi0, span, sqrt_label, private)
         field, keep_field = spectrum_field(tables)
         self.psi0, self.span = given.psi0, given.span
-        self._created(context, (self.sedges.size - 1, self.pedges.size - 1, self.gedges.size - 1), ctypes.byref(given),
-                      ctypes.byref(field), self.sedges.ctypes.data, self.sedges.size - 1, self.pedges.ctypes.data,
-                      self.pedges.size - 1, self.gedges.ctypes.data, self.gedges.size - 1)
+        self._created_cells(context, batches, (self.sedges.size - 1, self.pedges.size - 1, self.gedges.size - 1),
+                            ctypes.byref(given), ctypes.byref(field), self.sedges.ctypes.data, self.sedges.size - 1,
+                            self.pedges.ctypes.data, self.pedges.size - 1, self.gedges.ctypes.data, self.gedges.size - 1)
         del keep, keep_field                                 # the library has copied the tables
 
-    def like(self, context):
-        """An empty twin with this one's map, edges and options on another context."""
+    def _twin(self, context, batches):
         return PhaseDistribution(context, self.tables, self.sedges, self.pedges, self.gedges, self.psi0, self.span,
-                                 self.sqrt_label, self.private)
+                                 self.sqrt_label, self.private, batches)
 
     @property
     def label_kind(self):
@@ -95,20 +127,17 @@ class PhaseDistribution(ExactCells):
         self.context._check(self.lib.gfhip_phase_add(self.handle, keys, 0 if weight is None else key_of(weight),
                                                      int(weight is not None), int(count)))
 
+    def add_particles(self, x, y, z, ux, uy, uz, gamma, count, first, weight=None):
+        """add() for a distribution with batches: particle i of the buffers is particle first + i of the whole ensemble."""
+        keys = _keys((x, y, z, ux, uy, uz, gamma), 7)
+        self.context._check(self.lib.gfhip_phase_add_particles(self.handle, keys, 0 if weight is None else key_of(weight),
+                                                               int(weight is not None), int(count), int(first)))
+
     def coordinates(self, x, y, z, ux, uy, uz, gamma, label_key, pitch_key, count):
         """The labels and pitch cosines of `count` particles into the fp64 buffers `label_key` and `pitch_key` (NaN off
         the map); asynchronous."""
         keys = _keys((x, y, z, ux, uy, uz, gamma), 7)
         self.context._check(self.lib.gfhip_phase_coordinates(self.handle, keys, key_of(label_key), key_of(pitch_key), int(count)))
-
-    def merge(self, limbs, samples=0, outside=0, skipped=0):
-        """Add another distribution's state() and counts() (same map and edges: the caller's business); another shape is
-        refused."""
-        limbs = np.ascontiguousarray(limbs, dtype=np.int64)
-        if limbs.ndim != 4 or limbs.shape[-1] != LIMBS:
-            raise ValueError("merge: limbs of shape %r are no %r state" % (limbs.shape, self.shape + (LIMBS,)))
-        self.context._check(self.lib.gfhip_phase_merge(self.handle, limbs.ctypes.data, *limbs.shape[:-1], int(samples),
-                                                       int(outside), int(skipped)))
 
     def profile(self, context=None):
         """A FluxProfile on the label edges (on `context`, this distribution's by default) that holds the marginal over
@@ -116,10 +145,11 @@ class PhaseDistribution(ExactCells):
         distribution's: a particle that fell off the pitch or the gamma axis is among `outside`."""
         marginal = FluxProfile(context or self.context, self.tables, self.sedges, self.psi0, self.span, self.sqrt_label,
                                self.private)
-        state = self.state()
+        with self._plain() as plain:
+            state = plain.state()
         counts = self.counts()
-        for p in range(self.shape[1]):
-            for g in range(self.shape[2]):
+        for p in range(state.shape[1]):
+            for g in range(state.shape[2]):
                 marginal.merge(state[:, p, g, :], **(counts if p == 0 and g == 0 else {}))
         return marginal
 

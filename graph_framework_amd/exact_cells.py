@@ -2,6 +2,7 @@
 sums on a context's device, cells x 67 limbs of csrc/superacc.hpp and three counters, behind gfhip_bins_*, gfhip_flux_*
 or gfhip_spectrum_* (include/gf_hip.h).
 They differ in how a sample finds its cell, which is the constructor's business."""
+import contextlib
 import ctypes
 import os
 
@@ -63,7 +64,9 @@ class ExactCells:
 class RayBatches(ExactCells):
     """What a flux profile and a spectrum with batches=G add to ExactCells (batches.py, csrc/ray_batches.hpp): the state
     is batch-major, shape (G,) + the cells', slab g that of the samples of batch g's rays.  A subclass sets `batches`
-    (None: no batches) and `cell_shape` before `_created`, and has `_twin(context, batches)`."""
+    (None: no batches) and `cell_shape` before `_created`, and has `_twin(context, batches)`.  A distribution and a
+    moment profile of particles (distribution.py, moments.py) keep batches of particles the same way: read `particle`
+    for `ray` below, the particle's index in the whole ensemble."""
     batches = None
 
     def _created_cells(self, context, batches, cell_shape, *arguments):
@@ -104,6 +107,16 @@ class RayBatches(ExactCells):
             marginal.merge(state[g], **(counts if g == 0 else {}))
         return marginal
 
+    @contextlib.contextmanager
+    def _plain(self):
+        """This object, or, of one with batches, its total() for the length of the block."""
+        marginal = self if self.batches is None else self.total()
+        try:
+            yield marginal
+        finally:
+            if marginal is not self:
+                marginal.close()
+
     def batch_rays(self, first, count):
         """int64[batches]: the rays of [first, first + count) in every batch."""
         self._batched("batch_rays()")
@@ -132,6 +145,15 @@ class RayBatches(ExactCells):
         count): stderr, batch_bins (the batch means) and batch_rays."""
         _, stderr, _ = self.standard_error(first, count)
         return dict(stderr=stderr, batch_bins=self.batch_means(first, count), batch_rays=self.batch_rays(first, count))
+
+
+    def sum_error_variables(self, first, count):
+        """The keywords of write_phase_bins and write_moment_bins for the batch statistics of the particles [first,
+        first + count), for files whose bins are sums over the particles, not means: stderr, `count` times the standard
+        error of the mean per particle; batch_bins, the batch means; batch_particles."""
+        _, stderr, _ = self.standard_error(first, count)
+        return dict(stderr=float(count)*stderr, batch_bins=self.batch_means(first, count),
+                    batch_particles=self.batch_rays(first, count))
 
 
 def bin_files(grid, directory, num_files, tag, names=("x", "y", "z", "d_power"), first_ray=0):

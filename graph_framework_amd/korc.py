@@ -52,10 +52,13 @@ class Korc:
 
     items: optional {workload name: GFIR bytes} (received by broadcast from rank 0).
     device_state: keep the seven particle arrays in torch CUDA tensors (self.device) adopted by
-    the context, so that the output-cadence all-gather reads them in place."""
+    the context, so that the output-cadence all-gather reads them in place.
+    first_particle: the index of this shard's first particle in the whole ensemble, which bin() gives a distribution or
+    a moment profile with batches."""
 
-    def __init__(self, particles, dtype="f64", index=0, stream=None, items=None, device_state=False):
+    def __init__(self, particles, dtype="f64", index=0, stream=None, items=None, device_state=False, first_particle=0):
         self.dtype = dtype
+        self.first_particle = int(first_particle)
         self.np_dtype = _NP[dtype]
         sizes = [np.size(particles[k]) for k in PARTICLE if np.ndim(particles[k]) > 0]
         self.num_particles = max(sizes) if sizes else 1
@@ -96,10 +99,14 @@ class Korc:
     def bin(self, distribution, weight=None):
         """Bin the particles as they lie on the device into `distribution` (a distribution.PhaseDistribution made on
         self.work.context): enqueued on the push's stream behind the steps run so far, no synchronisation, no copy.
-        weight: the key of a buffer of this context with the push's dtype; every particle counts 1.0 without one."""
+        weight: the key of a buffer of this context with the push's dtype; every particle counts 1.0 without one.  One
+        made with batches takes the particles with their index in the ensemble, self.first_particle onwards."""
         if distribution.context is not self.work.context:
             raise ValueError("the distribution must be created on the push's context (push.work.context)")
-        distribution.add(*PARTICLE, self.num_particles, weight=weight)
+        if getattr(distribution, "batches", None) is not None:
+            distribution.add_particles(*PARTICLE, self.num_particles, self.first_particle, weight=weight)
+        else:
+            distribution.add(*PARTICLE, self.num_particles, weight=weight)
 
     def track(self, confinement, weight=None, exit=None):
         """Examine the particles as they lie on the device for first exits (a confinement.Confinement made on

@@ -21,7 +21,8 @@ import ctypes
 import numpy as np
 
 from .backend import GfHipError, key_of
-from .exact_cells import LIMBS, ExactCells
+from .batches import ratio_error_of
+from .exact_cells import LIMBS, RayBatches
 from .flux import FluxProfile, _Info, flux_map
 from .spectrum import _keys, spectrum_field
 
@@ -87,12 +88,42 @@ def add_host(tables, sedges, columns, weight=None, limbs=None, counters=None, ps
     return limbs, counters
 
 
-class FluxMoments(ExactCells):
+def add_particles_host(tables, sedges, batches, columns, first, weight=None, limbs=None, counters=None, psi0=None, span=None,
+                       sqrt_label=False):
+    """add_host per batch of particles (gfhip_moments_add_particles_host): particle i of the columns is particle first + i
+    of the ensemble.  (limbs (batches, ns, 4, 67) int64, counters (3,) uint64), the bytes and numbers of a FluxMoments
+    with batches after the same add_particles; given `limbs` and `counters`, added to in place."""
+    from . import _lib
+    lib = _lib.load()
+    given, keep = flux_map(tables, psi0, span, sqrt_label)
+    field, keep_field = spectrum_field(tables)
+    sedges = np.ascontiguousarray(sedges, dtype=np.float64).reshape(-1)
+    if sedges.size < 2:
+        raise ValueError("a moment profile needs at least two edges")
+    shape = (int(batches), sedges.size - 1, len(MOMENTS), LIMBS)
+    if limbs is None:
+        limbs, counters = np.zeros(shape, dtype=np.int64), np.zeros(3, dtype=np.uint64)
+    for name, array, kind, want in (("limbs", limbs, np.int64, shape), ("counters", counters, np.uint64, (3,))):
+        if not isinstance(array, np.ndarray) or array.dtype != kind or array.shape != want or not array.flags["C_CONTIGUOUS"]:
+            raise ValueError("%s must be a contiguous %s array of shape %r: it is updated in place" % (name, np.dtype(kind).name, want))
+    columns, is_f32 = _host_columns(columns, weight)
+    pointers = (ctypes.c_void_p*8)(*[column.ctypes.data for column in columns])
+    if lib.gfhip_moments_add_particles_host(ctypes.byref(given), ctypes.byref(field), sedges.ctypes.data, sedges.size - 1,
+                                            int(batches), pointers, int(is_f32), columns[0].size, int(first), limbs.ctypes.data,
+                                            counters.ctypes.data):
+        raise GfHipError(lib.gfhip_last_error(None).decode())
+    del keep, keep_field
+    return limbs, counters
+
+
+class FluxMoments(RayBatches):
     """Exact sums of the four MOMENTS per flux surface on a context's device (gfhip_moments_*, include/gf_hip.h); state()
-    is (ns, 4, 67), read() (ns, 4)."""
+    is (ns, 4, 67), read() (ns, 4).  batches=G: the same sums per batch of particles (batches.py, the particle's index in
+    the ensemble in place of a ray's), state() (G, ns, 4, 67), fed with add_particles; total() is the plain profile,
+    standard_error() the error bar of its cells and means_error() that of means()."""
     prefix = "moments"
 
-    def __init__(self, context, tables, sedges, psi0=None, span=None, sqrt_label=False, private=True):
+    def __init__(self, context, tables, sedges, psi0=None, span=None, sqrt_label=False, private=True, batches=None):
         self.tables = tables
         self.sedges = np.ascontiguousarray(sedges, dtype=np.float64).reshape(-1)
         if self.sedges.size < 2:
@@ -102,14 +133,17 @@ class FluxMoments(ExactCells):
         given, keep = flux_map(tables, psi0, span, sqrt_label, private)
         field, keep_field = spectrum_field(tables)
         self.psi0, self.span = given.psi0, given.span
-        self._created(context, (self.sedges.size - 1, len(MOMENTS)), ctypes.byref(given), ctypes.byref(field),
-                      self.sedges.ctypes.data, self.sedges.size - 1)
+        self._created_cells(context, batches, (self.sedges.size - 1, len(MOMENTS)), ctypes.byref(given), ctypes.byref(field),
+                            self.sedges.ctypes.data, self.sedges.size - 1)
         del keep, keep_field                                 # the library has copied the tables
 
-    def like(self, context, sedges=None):
-        """An empty twin with this one's map and options on another context (or on other label edges)."""
+    def _twin(self, context, batches, sedges=None):
         return FluxMoments(context, self.tables, self.sedges if sedges is None else sedges, self.psi0, self.span,
-                           self.sqrt_label, self.private)
+                           self.sqrt_label, self.private, batches)
+
+    def like(self, context, sedges=None):
+        """An empty twin with this one's map, options and batches on another context (or on other label edges)."""
+        return self._twin(context, self.batches, sedges)
 
     @property
     def label_kind(self):
@@ -123,28 +157,26 @@ class FluxMoments(ExactCells):
         self.context._check(self.lib.gfhip_moments_add(self.handle, keys, 0 if weight is None else key_of(weight),
                                                        int(weight is not None), int(count)))
 
+    def add_particles(self, x, y, z, ux, uy, uz, gamma, count, first, weight=None):
+        """add() for a profile with batches: particle i of the buffers is particle first + i of the whole ensemble."""
+        keys = _keys((x, y, z, ux, uy, uz, gamma), 7)
+        self.context._check(self.lib.gfhip_moments_add_particles(self.handle, keys, 0 if weight is None else key_of(weight),
+                                                                 int(weight is not None), int(count), int(first)))
+
     def values(self, x, y, z, ux, uy, uz, gamma, label_key, values_key, count):
         """The labels of `count` particles into the fp64 buffer `label_key` and their four moments into the fp64 buffer
         `values_key` (4*count, [particle][k]), NaN off the map; asynchronous."""
         keys = _keys((x, y, z, ux, uy, uz, gamma), 7)
         self.context._check(self.lib.gfhip_moments_values(self.handle, keys, key_of(label_key), key_of(values_key), int(count)))
 
-    def merge(self, limbs, samples=0, outside=0, skipped=0):
-        """Add another moment profile's state() and counts() (same map and edges: the caller's business); another shape
-        is refused."""
-        limbs = np.ascontiguousarray(limbs, dtype=np.int64)
-        if limbs.ndim != 3 or limbs.shape[-1] != LIMBS:
-            raise ValueError("merge: limbs of shape %r are no %r state" % (limbs.shape, self.shape + (LIMBS,)))
-        self.context._check(self.lib.gfhip_moments_merge(self.handle, limbs.ctypes.data, *limbs.shape[:-1], int(samples),
-                                                         int(outside), int(skipped)))
-
     def totals(self):
         """(4,): the exact marginal over the surfaces, the ns slices state()[s] merged into a one-surface twin on the
         first and the last edge and rounded once."""
-        state = self.state()
-        twin = self.like(self.context, self.sedges[[0, -1]])
+        with self._plain() as plain:
+            state = plain.state()
+        twin = self._twin(self.context, None, self.sedges[[0, -1]])
         try:
-            for s in range(self.shape[0]):
+            for s in range(state.shape[0]):
                 twin.merge(state[s:s + 1])
             return twin.read()[0]
         finally:
@@ -156,14 +188,24 @@ class FluxMoments(ExactCells):
         weights."""
         marginal = FluxProfile(context or self.context, self.tables, self.sedges, self.psi0, self.span, self.sqrt_label,
                                self.private)
-        marginal.merge(self.state()[:, 0, :], **self.counts())
+        with self._plain() as plain:
+            marginal.merge(plain.state()[:, 0, :], **plain.counts())
         return marginal
 
     def means(self):
         """(ns, 3): current, energy and radiation per unit of weight, read()[:, 1:]/read()[:, :1]; NaN where empty."""
-        bins = self.read()
+        with self._plain() as plain:
+            bins = plain.read()
         with np.errstate(divide="ignore", invalid="ignore"):
             return np.where(bins[:, :1] == 0.0, np.nan, bins[:, 1:]/bins[:, :1])
+
+    def means_error(self):
+        """(ns, 3): the standard error of means() of a profile with batches, the delete-one-batch jackknife of the ratio
+        of current, energy and radiation to the density (batches.ratio_error_of); NaN with fewer than two batches that
+        reached the surface."""
+        self._batched("means_error()")
+        sums = self.read()
+        return np.stack([ratio_error_of(sums[:, :, k], sums[:, :, 0]) for k in (1, 2, 3)], axis=1)
 
     def volumes(self, sub=16):
         """The volumes in m^3 of a FluxProfile on the same edges (FluxProfile.volumes)."""
@@ -177,8 +219,10 @@ class FluxMoments(ExactCells):
         """(ns, 4): read()/volume per surface, the number density, j_par(s), the energy density and the radiated power
         density; NaN where no quadrature point reached the cell."""
         volume = self.volumes(sub)[:, None]
+        with self._plain() as plain:
+            bins = plain.read()
         with np.errstate(divide="ignore", invalid="ignore"):
-            return np.where(volume == 0.0, np.nan, self.read()/volume)
+            return np.where(volume == 0.0, np.nan, bins/volume)
 
     def info(self):
         """How deposits are launched: {private_sums, workgroup_size, cap_cells, max_workgroups, lds_bytes}."""

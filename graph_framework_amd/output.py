@@ -479,18 +479,74 @@ def write_spectrum_bins(path, bins, sbins, nbins, psi0, span, label="s", c=1.0, 
     file.close()
 
 
+def _snapshot_batches(cell_shape, times, stderr, batch_bins, batch_particles, means_stderr=None):
+    """The batch statistics of the snapshots of a particle tally (batches.py), each optional, checked and shaped before
+    the file is made: stderr (time,) + cells; batch_bins (time, nb) + cells, the batch means; batch_particles (time, nb) or
+    (nb,), the particles of every batch; means_stderr (time, ns, 3).  One snapshot may leave the time axis out."""
+    cell_shape = tuple(cell_shape)
+    out = {}
+    if stderr is not None:
+        stderr = np.asarray(stderr, dtype=np.float64)
+        stderr = stderr[None] if stderr.ndim == len(cell_shape) else stderr
+        if stderr.shape != (times,) + cell_shape:
+            raise ValueError("stderr of shape %r where the bins are %r" % (stderr.shape, (times,) + cell_shape))
+        out["stderr"] = stderr
+    if means_stderr is not None:
+        means_stderr = np.asarray(means_stderr, dtype=np.float64)
+        means_stderr = means_stderr[None] if means_stderr.ndim == 2 else means_stderr
+        if means_stderr.shape != (times, cell_shape[0], cell_shape[1] - 1):
+            raise ValueError("means_stderr of shape %r where the bins are %r" % (means_stderr.shape, (times,) + cell_shape))
+        out["means_stderr"] = means_stderr
+    if batch_bins is not None:
+        batch_bins = np.asarray(batch_bins, dtype=np.float64)
+        batch_bins = batch_bins[None] if batch_bins.ndim == len(cell_shape) + 1 else batch_bins
+        if batch_bins.ndim != len(cell_shape) + 2 or batch_bins.shape[0] != times or batch_bins.shape[2:] != cell_shape:
+            raise ValueError("batch_bins of shape %r where the bins are %r" % (batch_bins.shape, (times,) + cell_shape))
+        out["batch_bins"] = batch_bins
+    if batch_particles is not None:
+        batch_particles = np.asarray(batch_particles, dtype=np.float64)
+        if batch_particles.ndim == 1:
+            batch_particles = np.broadcast_to(batch_particles, (times, batch_particles.size)).copy()
+        if batch_particles.ndim != 2 or batch_particles.shape[0] != times:
+            raise ValueError("batch_particles of shape %r for %d snapshots" % (batch_particles.shape, times))
+        out["batch_particles"] = batch_particles
+    if len({v.shape[1] for k, v in out.items() if k.startswith("batch_")}) > 1:
+        raise ValueError("batch_bins and batch_particles differ in their number of batches")
+    return out
+
+
+def _write_snapshot_batches(file, cell_dimensions, given):
+    """What _snapshot_batches made, written last: a file without them is the file it was."""
+    batched = [v for k, v in given.items() if k.startswith("batch_")]
+    if batched:
+        file.create_dimension("nb", batched[0].shape[1])
+    if "stderr" in given:
+        file.write_variable("stderr", given["stderr"], ("time",) + cell_dimensions)
+    if "means_stderr" in given:
+        file.create_dimension("nr", given["means_stderr"].shape[2])
+        file.write_variable("means_stderr", given["means_stderr"], ("time", cell_dimensions[0], "nr"))
+    if "batch_bins" in given:
+        file.write_variable("batch_bins", given["batch_bins"], ("time", "nb") + cell_dimensions)
+    if "batch_particles" in given:
+        file.write_variable("batch_particles", given["batch_particles"], ("time", "nb"))
+
+
 def write_phase_bins(path, bins, sbins, pbins, gbins, psi0, span, label="s", steps=None, samples=None, outside=None,
-                     skipped=None):
+                     skipped=None, stderr=None, batch_bins=None, batch_particles=None):
     """phase_bins.nc, the snapshots of a particle distribution (distribution.py): dimensions time, ns, nsp, np, npp, ng,
     ngp; f8 variables bins(time, ns, np, ng), sbins(nsp), pbins(npp) and gbins(ngp), the edges in the label, the pitch
     cosine and gamma; steps(time), the push's step count at every snapshot, and samples(time), outside(time),
     skipped(time), what became of its particles (f8, as every variable; zeros when not given); psi0 and span (f8) and the
-    label kind as global attributes.  A single (ns, np, ng) array is one snapshot."""
+    label kind as global attributes.  A single (ns, np, ng) array is one snapshot.  With stderr, batch_bins,
+    batch_particles (each optional; a distribution with batches) also the f8 variables stderr(time, ns, np, ng), the
+    standard error of bins, batch_bins(time, nb, ns, np, ng), the batch means, and batch_particles(time, nb) on a
+    dimension nb."""
     bins = np.asarray(bins)
     if bins.ndim == 3:
         bins = bins[None]
     if bins.ndim != 4:
         raise ValueError("a distribution's bins are (time, ns, np, ng)")
+    batch_variables = _snapshot_batches(bins.shape[1:], bins.shape[0], stderr, batch_bins, batch_particles)
     file = BinsFile(path)
     file.create_dimension("time", bins.shape[0])
     for name, length in zip(("ns", "np", "ng"), bins.shape[1:]):
@@ -505,11 +561,13 @@ def write_phase_bins(path, bins, sbins, pbins, gbins, psi0, span, label="s", ste
     file.float64_attribute("psi0", psi0)
     file.float64_attribute("span", span)
     file.text_attribute("label", label)
+    _write_snapshot_batches(file, ("ns", "np", "ng"), batch_variables)
     file.close()
 
 
 def write_moment_bins(path, bins, sbins, psi0, span, label="s", totals=None, steps=None, samples=None, outside=None, skipped=None,
-                      volume=None, density=None, sub=None, moments=("density", "current", "energy", "radiation")):
+                      volume=None, density=None, sub=None, moments=("density", "current", "energy", "radiation"), stderr=None,
+                      batch_bins=None, batch_particles=None, means_stderr=None):
     """moment_bins.nc, the snapshots of a push's moments per flux surface (moments.py), laid out as phase_bins.nc:
     dimensions time, ns, nsp, nm; f8 variables bins(time, ns, nm), the sums per surface and moment, totals(time, nm), their
     exact sums over the surfaces (bins summed when not given), sbins(nsp), the edges in the label; steps(time), the push's
@@ -517,7 +575,10 @@ def write_moment_bins(path, bins, sbins, psi0, span, label="s", totals=None, ste
     every variable; zeros when not given); the moments' names (comma separated), their units ("normalised": the push's,
     no physical constants), psi0 and span (f8) and the label kind as global attributes.  With `volume` (ns) and `density`
     (time, ns, nm) (both or neither) also those variables, the cells' volumes in m^3 and bins/volume, and the quadrature's
-    sub as an integer attribute.  A single (ns, nm) array is one snapshot."""
+    sub as an integer attribute.  A single (ns, nm) array is one snapshot.  With stderr, batch_bins, batch_particles,
+    means_stderr (each optional; a profile with batches) also the f8 variables stderr(time, ns, nm), batch_bins(time, nb,
+    ns, nm), the batch means, batch_particles(time, nb) and means_stderr(time, ns, nr), the jackknife error of the nr = nm
+    - 1 moments per unit of density (FluxMoments.means_error)."""
     if (volume is None) != (density is None):
         raise ValueError("volume and density go together")
     if volume is not None and sub is None:
@@ -538,6 +599,7 @@ def write_moment_bins(path, bins, sbins, psi0, span, label="s", totals=None, ste
         density = density[None] if density.ndim == 2 else density
         if density.shape != bins.shape or np.size(volume) != bins.shape[1]:
             raise ValueError("density has the bins' shape and volume one entry per surface")
+    batch_variables = _snapshot_batches(bins.shape[1:], bins.shape[0], stderr, batch_bins, batch_particles, means_stderr)
     file = BinsFile(path)
     for name, length in (("time", bins.shape[0]), ("ns", bins.shape[1]), ("nsp", bins.shape[1] + 1), ("nm", bins.shape[2])):
         file.create_dimension(name, length)
@@ -556,6 +618,7 @@ def write_moment_bins(path, bins, sbins, psi0, span, label="s", totals=None, ste
     file.float64_attribute("psi0", psi0)
     file.float64_attribute("span", span)
     file.text_attribute("label", label)
+    _write_snapshot_batches(file, ("ns", "nm"), batch_variables)
     file.close()
 
 

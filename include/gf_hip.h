@@ -531,7 +531,13 @@ int gfhip_spectrum_merge_batches(gfhip_spectrum *spectrum, const int64_t *limbs,
  * gedges[ig] <= gamma < gedges[ig+1].  The last edge of an axis is outside it: pitch edges that should hold xi = 1
  * end above 1 (the Python helper pitch_edges(n) ends at nextafter(1, 2)).  It deposits its weight, an eighth column
  * of the same type, or 1.0 without one.  `outside`: off the map, off any axis, or a NaN label, xi or gamma; `skipped`:
- * inside with a NaN or infinite weight.  There are no batches of rays here: particles are no Monte-Carlo rays.
+ * inside with a NaN or infinite weight.
+ *
+ * Batches of particles: a cell is a Monte-Carlo estimate over the pushed particles, and its standard error comes
+ * from the same tally kept per batch of particles.  The rule is that of the batches of rays (gfhip_flux_create_batched,
+ * csrc/ray_batches.hpp) with the particle's index p in the whole ensemble, over all ranks and shards, in place of the
+ * ray's: batch (p >> 6) % G.  A batched distribution has the state (G, ns, np, ng, 67), slab g the state of a plain
+ * distribution fed batch g's particles alone with the same weights; the counters are those of all particles.
  *
  * gfhip_phase_create: as gfhip_spectrum_create with three edge arrays; the field's c is ignored.  Refused: what
  *   gfhip_flux_create refuses for the map and gfhip_spectrum_create for the field (c apart); an axis outside 1-4096
@@ -546,7 +552,17 @@ int gfhip_spectrum_merge_batches(gfhip_spectrum *spectrum, const int64_t *limbs,
  * gfhip_phase_counts / _state / _read / _info / _destroy: as the spectrum's; _merge takes the three cell counts of the
  *   incoming state and refuses another shape.
  * gfhip_phase_coordinates_host: no device, no context; the same lines on the CPU from the caller's tables, the seven
- *   columns float when is_f32 is non-zero and double otherwise.  Errors: gfhip_last_error(NULL). */
+ *   columns float when is_f32 is non-zero and double otherwise.  Errors: gfhip_last_error(NULL).
+ * gfhip_phase_create_batched: gfhip_phase_create with 1 <= batches <= 256 and batches*ns*np*ng <= 2^20.  A workgroup
+ *   sums one batch at a time, so the LDS path is taken up to 256 cells PER BATCH; gfhip_phase_info describes that launch.
+ * gfhip_phase_add_particles: gfhip_phase_add for a batched distribution: particle i of the buffers is particle
+ *   first_particle + i.  Refused before any launch: what gfhip_phase_add refuses; a distribution without batches;
+ *   first_particle + count overflowing 64 bits.  gfhip_phase_add refuses a batched distribution.
+ * gfhip_phase_merge_batches: gfhip_phase_merge for a batched distribution; it takes the batches and the three cell
+ *   counts of the incoming state and refuses another shape or a distribution without batches; gfhip_phase_merge
+ *   refuses a batched one.  _counts, _state, _read, _info and _destroy serve both kinds, _state and _read batch-major.
+ * gfhip_phase_add_particles_host: no device, no context; the batched deposit on the CPU (csrc/phase_host.hpp) into
+ *   `limbs` (batches*ns*np*ng*67, canonical on return) and `counters` (3), columns[7] NULL without weights. */
 typedef struct gfhip_phase gfhip_phase;
 
 gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
@@ -562,6 +578,17 @@ int gfhip_phase_info(gfhip_phase *phase, struct gfhip_flux_info *info);
 void gfhip_phase_destroy(gfhip_phase *phase);
 int gfhip_phase_coordinates_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
                                  const void *const columns[7], int is_f32, size_t count, double *label, double *pitch);
+gfhip_phase *gfhip_phase_create_batched(gfhip_context *ctx, const struct gfhip_flux_map *map,
+                                        const struct gfhip_spectrum_field *field, const double *sedges, size_t ns,
+                                        const double *pedges, size_t np, const double *gedges, size_t ng, size_t batches);
+int gfhip_phase_add_particles(gfhip_phase *phase, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count,
+                              uint64_t first_particle);
+int gfhip_phase_merge_batches(gfhip_phase *phase, const int64_t *limbs, size_t batches, size_t ns, size_t np, size_t ng,
+                              uint64_t samples, uint64_t outside, uint64_t skipped);
+int gfhip_phase_add_particles_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                                   const double *sedges, size_t ns, const double *pedges, size_t np, const double *gedges,
+                                   size_t ng, size_t batches, const void *const columns[8], int is_f32, size_t count,
+                                   uint64_t first_particle, int64_t *limbs, uint64_t counters[3]);
 
 /* First-exit tracking of the particles of one push: which particles have left the plasma, at which step, where they
  * crossed and at what energy, kept on the device from one check to the next (csrc/confinement.hip).
@@ -655,7 +682,12 @@ int gfhip_confine_check_host(const struct gfhip_flux_map *map, double limit, con
  * gfhip_moments_values_host, gfhip_moments_add_host: no device, no context; the same lines on the CPU from the caller's
  *   tables and arrays (csrc/moments_host.hpp), the columns float when is_f32 is non-zero and double otherwise,
  *   columns[7] NULL without weights.  add_host adds to `limbs` (ns*4*67, canonical on return) and `counters` (3).
- *   Errors: gfhip_last_error(NULL). */
+ *   Errors: gfhip_last_error(NULL).
+ * gfhip_moments_create_batched, gfhip_moments_add_particles, gfhip_moments_merge_batches (which takes batches, ns, nm)
+ *   and gfhip_moments_add_particles_host: the batches of particles of gfhip_phase_create_batched for a moment profile,
+ *   state (G, ns, 4, 67), batches*ns*4 <= 2^20, the LDS path up to 64 surfaces PER BATCH.  A particle deposits all
+ *   four of its values into its batch's slab or none; the counters count the particles of all batches.  The refusals are
+ *   those of the distribution's calls, and count = 0 as gfhip_moments_add. */
 #define GFHIP_MOMENTS 4
 #define GFHIP_MOMENT_DENSITY 0
 #define GFHIP_MOMENT_CURRENT 1
@@ -679,6 +711,16 @@ int gfhip_moments_values_host(const struct gfhip_flux_map *map, const struct gfh
 int gfhip_moments_add_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field, const double *sedges,
                            size_t ns, const void *const columns[8], int is_f32, size_t count, int64_t *limbs,
                            uint64_t counters[3]);
+gfhip_moments *gfhip_moments_create_batched(gfhip_context *ctx, const struct gfhip_flux_map *map,
+                                            const struct gfhip_spectrum_field *field, const double *sedges, size_t ns,
+                                            size_t batches);
+int gfhip_moments_add_particles(gfhip_moments *moments, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count,
+                                uint64_t first_particle);
+int gfhip_moments_merge_batches(gfhip_moments *moments, const int64_t *limbs, size_t batches, size_t ns, size_t nm,
+                                uint64_t samples, uint64_t outside, uint64_t skipped);
+int gfhip_moments_add_particles_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                                     const double *sedges, size_t ns, size_t batches, const void *const columns[8], int is_f32,
+                                     size_t count, uint64_t first_particle, int64_t *limbs, uint64_t counters[3]);
 
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
