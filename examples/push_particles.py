@@ -18,10 +18,15 @@ moments' file means_stderr as well, the error of the moments per unit of density
     python examples/push_particles.py --particles 1000000 --loss-limit 0.06 --loss-bins 32,32,8 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
     python examples/push_particles.py --particles 1000000 --moments 32 --moments-density 8 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
     python examples/push_particles.py --particles 1000000 --moments 32 --particle-batches 64 --loss-limit 0.06 --flux-tables tests/golden/efit_tables.npz --output /tmp/korc
+    python examples/push_particles.py --particles 1000000 --load-label-range 0,0.3 --load-box 1.2,2.3,-1,1 --load-speed 0.3,0.9 --flux-tables tests/golden/efit_tables.npz
 
 The start positions are spread around the axis and the start momenta in size and pitch, seeded.  The push conserves gamma
 in a static field: the largest change of the gamma marginal between the first and the last snapshot is printed, the first
 thing to check after a run.  The pitch axis is pitch_edges(--pitch-bins): uniform on [-1, 1], its last edge just above 1.
+With --load-label-range LOW,HIGH the ensemble comes from a particle source instead (graph_framework_amd/source.py): drawn
+on the device, uniform in volume between the two flux surfaces inside --load-box, speeds of --load-speed and pitches of
+--load-pitch against the local field.  A particle that found no position in --load-attempts candidates is unplaced and
+takes no part: its `placed` column is the weight of every snapshot (a tracker counts it lost at the first check).
 """
 import argparse
 import os
@@ -87,6 +92,13 @@ def main():
                         help="with --moments: the file also gets the surfaces' volumes (quadrature SUB) and the moments per volume")
     parser.add_argument("--particle-batches", type=int, default=None, metavar="G",
                         help="keep the distribution and the moments per batch of particles, 1 to 256: error bars")
+    parser.add_argument("--load-label-range", type=pair, default=None, metavar="LOW,HIGH",
+                        help="draw the ensemble on the device, uniform in volume between these two flux labels")
+    parser.add_argument("--load-box", type=box, default=None, metavar="RLO,RHI,ZLO,ZHI",
+                        help="with --load-label-range: where positions are tried (default: the map)")
+    parser.add_argument("--load-speed", type=pair, default=(0.3, 0.9), metavar="LOW,HIGH", help="|v|/c of the loaded particles")
+    parser.add_argument("--load-pitch", type=pair, default=(-1.0, 1.0), metavar="LOW,HIGH", help="their pitch cosine to the local field")
+    parser.add_argument("--load-attempts", type=int, default=64, help="positions tried per particle before it stays unplaced")
     parser.add_argument("--flux-tables", required=True, help="an .npz with efit.nc's psi and fpol tables (tests/golden/efit_tables.npz)")
     parser.add_argument("--output", default=None, help="prefix of <output>_phase_bins.nc (default: no file)")
     parser.add_argument("--seed", type=int, default=0)
@@ -108,8 +120,21 @@ def main():
     sedges = np.linspace(*args.label_range, args.label_bins + 1)
     pedges = pitch_edges(args.pitch_bins)
     gedges = np.linspace(*args.gamma_range, args.gamma_bins + 1)
-    push = korc.Korc(ensemble(args.particles, args.seed), args.dtype, index=args.device)
+    loaded = args.load_label_range is not None
+    push = korc.Korc(korc.blank(args.particles) if loaded else ensemble(args.particles, args.seed), args.dtype, index=args.device)
     push.compile()
+    placed_key = None
+    if loaded:
+        from graph_framework_amd.source import ParticleSource
+        numr, numz = tables["psi_c00"].shape
+        rmin, dr, zmin, dz = (float(tables[k]) for k in ("rmin", "dr", "zmin", "dz"))
+        source = ParticleSource(push.work.context, tables, args.load_box or (rmin, rmin + numr*dr, zmin, zmin + numz*dz),
+                                args.load_label_range, args.load_speed, args.load_pitch, seed=args.seed,
+                                attempts=args.load_attempts, dtype=args.dtype, sqrt_label=args.sqrt_label)
+        placed_key = "placed"
+        push.load(source, placed=placed_key)
+        load_counts = source.counts()
+        source.close()
     push.pre_run()
     tracker = None
     if args.loss_limit is not None:
@@ -135,12 +160,13 @@ def main():
                                      batches=args.particle_batches)
         if tracker is not None:
             push.track(tracker)                              # settles the particles that have left since the last snapshot
-        push.bin(snapshot, weight=tracker.alive_key if tracker is not None else None)        # behind the steps on the push's stream; the particles stay put
+        weight = tracker.alive_key if tracker is not None else placed_key
+        push.bin(snapshot, weight=weight)                    # behind the steps on the push's stream; the particles stay put
         snapshots.append(snapshot)
         steps.append(done)
         if args.moments is not None:
             profiles.append(FluxMoments(push.work.context, tables, medges, sqrt_label=args.sqrt_label, batches=args.particle_batches))
-            push.bin(profiles[-1], weight=tracker.alive_key if tracker is not None else None)
+            push.bin(profiles[-1], weight=weight)
     batched = args.particle_batches is not None
     errors, moment_errors = {}, {}
     if batched:
@@ -176,6 +202,10 @@ def main():
 
     print("%d particles (%s), %d steps, %d snapshots on %dx%dx%d cells of %s, xi and gamma"
           % (args.particles, args.dtype, done, len(steps), args.label_bins, args.pitch_bins, args.gamma_bins, kind))
+    if loaded:
+        print("loaded between %s = %g and %g: %d placed, %d unplaced, %.3f position attempts per particle"
+              % ((kind,) + tuple(args.load_label_range) + (load_counts["placed"], load_counts["unplaced"],
+                                                           load_counts["position_tries"]/args.particles)))
     for step, count, snapshot in zip(steps, counts, bins):
         print("  step %6d: %d in a cell, %d outside, %d skipped" % (step, int(snapshot.sum()), count["outside"], count["skipped"]))
     marginal = bins.sum(axis=(1, 2))                         # (time, ng): small integers, exact in fp64

@@ -158,6 +158,13 @@ SYMBOLS = [
     ("gfhip_moments_merge_batches", _I, [_P, _P, _S, _S, _S, _U64, _U64, _U64]),
     ("gfhip_moments_add_particles_host", _I, [_P, _P, _P, _S, _S, _P, _I, _S, _U64, _P, _P]),
     ("gfhip_exact_sum", _I, [_P, _S, ctypes.POINTER(ctypes.c_double), _P]),
+    ("gfhip_source_create", _P, [_P, _P, _P, _P] + [ctypes.c_double]*6 + [_P, _P, _S, _U64, _U32, _I, _U32, _S]),
+    ("gfhip_source_fill", _I, [_P, _P, _U64, _I, _U64, _S]),
+    ("gfhip_source_counts", _I, [_P, _P]),
+    ("gfhip_source_info", _I, [_P, _P]),
+    ("gfhip_source_destroy", None, [_P]),
+    ("gfhip_source_fill_host", _I, [_P, _P, _P] + [ctypes.c_double]*6 + [_P, _P, _S, _U64, _U32, _U32, _P, _I, _U64, _S, _P]),
+    ("gfhip_source_block_host", None, [_P, _P, _P]),
 ]
 
 _lib = None

@@ -1,7 +1,7 @@
 //------------------------------------------------------------------------------
 ///  @file cell_launch.hpp
-///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip, flux_spectrum.hip, phase_bins.hip, moment_bins.hip and
-///  confinement.hip.
+///  @brief What gf_hip.cpp launches of deposition.hip, flux_profile.hip, flux_spectrum.hip, phase_bins.hip, moment_bins.hip,
+///  confinement.hip and particle_source.hip.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_CELL_LAUNCH_HPP
 #define GFHIP_CELL_LAUNCH_HPP
@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "flux_label.hpp"
+#include "particle_draw.hpp"
 
 namespace gfhip {
 
@@ -120,6 +121,16 @@ void launch_confinement_check(const void *const *columns, void *alive, const boo
 //  The sentinel into lost_step and 1 into alive (both null: left alone), NaN into the exit buffers (both null: none).
 void launch_confinement_reset(const size_t count, uint32_t *lost_step, void *alive, const bool is_f32, double *exit_r,
                               double *exit_z, hipStream_t stream);
+
+//  particle_source.hip.  columns: x, y, z, ux, uy, uz, gamma, all float when is_f32 and all double otherwise, and `placed`
+//  of the same type (null: none): element i receives particle first_particle + i.  profile: the par.ns + 1 edges, then the
+//  par.ns probabilities (unread when par.ns = 0), scale = ns/(last edge - first edge).  counters: placed, unplaced,
+//  position_tries, gyro_tries.  max_workgroups: of 256 lanes.
+void launch_particle_source(void *const *columns, void *placed, const bool is_f32, const size_t count,
+                            const unsigned long long first_particle, const flux::map &m, const flux::field &f,
+                            const draw::parameters &par, const double *packed, const double *fpol, const double *profile,
+                            const double scale, const bool refill, const size_t max_workgroups, unsigned long long *counters,
+                            hipStream_t stream);
 
 }  // namespace gfhip
 

@@ -41,6 +41,7 @@
 #include "moments_host.hpp"
 #include "phase_host.hpp"
 #include "ray_batches.hpp"
+#include "source_host.hpp"
 #include "superacc.hpp"
 
 namespace gfhip {
@@ -146,6 +147,7 @@ struct gfhip_context {
     std::vector<std::unique_ptr<gfhip_phase>> phases;          // distributions (gfhip_phase_create), until gfhip_phase_destroy
     std::vector<std::unique_ptr<gfhip_confine>> confines;      // trackers (gfhip_confine_create), until gfhip_confine_destroy
     std::vector<std::unique_ptr<gfhip_moments>> moments;       // moment profiles (gfhip_moments_create), until gfhip_moments_destroy
+    std::vector<std::unique_ptr<gfhip_source>> sources;        // particle sources (gfhip_source_create), until gfhip_source_destroy
     std::string error;
     gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
     gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
@@ -299,6 +301,20 @@ struct gfhip_moments : flux_cells {
     size_t ns = 0;
     double sscale = 0.0;
     device_ptr<double> fpol;
+};
+
+//  A particle source (particle_source.hip): the map and the field as a distribution holds them, the profile's edges and
+//  then its probabilities, and the counters placed, unplaced, position_tries, gyro_tries.
+struct gfhip_source {
+    gfhip_context *ctx = nullptr;
+    gfhip::flux::map map = {};
+    gfhip::flux::field field = {};
+    gfhip::draw::parameters par = {};
+    device_ptr<double> packed, fpol, profile;
+    double scale = 0.0;                                // ns/(last edge - first edge)
+    bool is_f32 = false, refill = false;
+    size_t max_workgroups = 0;
+    device_ptr<unsigned long long> counters;
 };
 
 #define GFHIP_TRY(ctx, call, what) do { if ((ctx)->check((call), (what))) return 1; } while (0)
@@ -1801,6 +1817,21 @@ static const char *flux_map_of(const gfhip_flux_map *given, gfhip::flux::map &m)
     return nullptr;
 }
 
+//  The 16 psi tables as [table cell][16]: a lane's coefficients are one 128-byte line.  False: no memory.
+static bool psi_lines(const gfhip_flux_map *given, std::vector<double> &lines) {
+    const size_t table = static_cast<size_t> (given->numr*given->numz);
+    try {
+        lines.resize(table*16);
+    } catch (const std::bad_alloc &) {
+        return false;
+    }
+    for (size_t k = 0; k < 16; k++) {
+        const double *from = given->coefficients + k*table;
+        for (size_t at = 0; at < table; at++) lines[at*16 + k] = from[at];
+    }
+    return true;
+}
+
 //  The map checked and copied, its tables repacked to [table cell][16] (a lane's coefficients are one 128-byte line) and
 //  uploaded with the edges, the launch shape decided and the `count` cells allocated.  prepare: the deposit kernels'
 //  request for large dynamic LDS, made when the private path is taken.
@@ -1813,17 +1844,8 @@ int flux_cells::create(gfhip_context *context, const gfhip_flux_map *given, cons
     slab = count;
     gfhip::flux_launch_shape(count, all_edges.size(), !(given->flags & gfhip::flux::flag_no_private_sums), context->num_cus,
                              &is_private, &cap, &block, &max_workgroups, &lds_bytes);
-    const size_t table = static_cast<size_t> (given->numr*given->numz);
     std::vector<double> lines;
-    try {
-        lines.resize(table*16);
-    } catch (const std::bad_alloc &) {
-        return context->fail("a flux map's tables do not fit the host's memory");
-    }
-    for (size_t k = 0; k < 16; k++) {
-        const double *from = given->coefficients + k*table;
-        for (size_t at = 0; at < table; at++) lines[at*16 + k] = from[at];
-    }
+    if (!psi_lines(given, lines)) return context->fail("a flux map's tables do not fit the host's memory");
     return context->check(allocate(packed, lines.size()*sizeof(double)), "hipMalloc(flux tables)") ||
            context->check(hipMemcpy(packed.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
            context->check(allocate(edges, all_edges.size()*sizeof(double)), "hipMalloc(edges)") ||
@@ -2968,6 +2990,182 @@ extern "C" int gfhip_confine_check_host(const gfhip_flux_map *map, double limit,
                                     exit_z, newly_lost, limbs, counters);
     }
     return 0;
+}
+
+//  Particle sources (particle_source.hip, particle_draw.hpp).
+
+//  The route of a source made with neither route flag.
+static const bool source_refill_by_default = true;
+
+//  What the rule needs beside the map and the field, or why a source is refused.
+static const char *source_parameters_of(const double *box, const double slo, const double shi, const double blo, const double bhi,
+                                        const double xlo, const double xhi, const double *sedges, const double *accept,
+                                        const size_t ns, const uint64_t seed, const uint32_t attempts, const uint32_t flags,
+                                        gfhip::draw::parameters &par) {
+    if (!box) return "a particle source needs its box {rlo, rhi, zlo, zhi}";
+    for (int k = 0; k < 4; k++) {
+        if (!std::isfinite(box[k])) return "the box of a particle source must be finite";
+    }
+    if (!(box[0] < box[1]) || !(box[2] < box[3]) || box[0] < 0.0) return "the box of a particle source needs 0 <= rlo < rhi and zlo < zhi";
+    if (!(slo < shi)) return "the label range of a particle source must not be empty or NaN";
+    if (!(blo < bhi) || !(blo >= 0.0) || !(bhi < 1.0)) return "the speed range of a particle source needs 0 <= blo < bhi < 1";
+    if (!(xlo < xhi) || !(xlo >= -1.0) || !(xhi <= 1.0)) return "the pitch range of a particle source needs -1 <= xlo < xhi <= 1";
+    if (attempts == 0 || attempts > gfhip::draw::max_attempts) return "a particle source makes 1 to 4096 attempts";
+    if (ns > static_cast<size_t> (gfhip::draw::max_profile_cells)) return "the profile of a particle source has at most 256 cells";
+    if ((ns != 0) != (sedges != nullptr) || (ns != 0) != (accept != nullptr)) {
+        return "the profile of a particle source is ns + 1 edges and ns probabilities, or neither with ns = 0";
+    }
+    if (ns && !edges_increase(sedges, ns)) return "the edges of a particle source's profile must be finite and strictly increasing";
+    for (size_t k = 0; k < ns; k++) {
+        if (!(accept[k] >= 0.0 && accept[k] <= 1.0)) return "the probabilities of a particle source's profile lie in [0, 1]";
+    }
+    if (flags & ~gfhip::draw::known_flags) return "unknown flag bits for a particle source";
+    if ((flags & gfhip::draw::known_flags) == gfhip::draw::known_flags) return "a particle source takes one route, plain or refill";
+    par = gfhip::draw::parameters_of(box, slo, shi, blo, bhi, xlo, xhi, seed, attempts, static_cast<int> (ns));
+    return nullptr;
+}
+
+extern "C" gfhip_source *gfhip_source_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
+                                             const double box[4], double slo, double shi, double blo, double bhi, double xlo,
+                                             double xhi, const double *sedges, const double *accept, size_t ns, uint64_t seed,
+                                             uint32_t attempts, int is_f32, uint32_t flags, size_t max_workgroups) {
+    if (!ctx) return nullptr;
+    if (!map || !field) {
+        ctx->fail("a particle source needs a map and a field");
+        return nullptr;
+    }
+    std::unique_ptr<gfhip_source> s(new gfhip_source);
+    const char *refused = flux_map_of(map, s->map);
+    if (!refused) refused = phase_field_of(field, s->field);
+    if (!refused) refused = source_parameters_of(box, slo, shi, blo, bhi, xlo, xhi, sedges, accept, ns, seed, attempts, flags, s->par);
+    if (refused) {
+        ctx->fail(refused);
+        return nullptr;
+    }
+    s->ctx = ctx;
+    s->is_f32 = is_f32 != 0;
+    s->refill = flags & gfhip::draw::known_flags ? (flags & gfhip::draw::flag_refill) != 0 : source_refill_by_default;
+    s->max_workgroups = max_workgroups ? max_workgroups : static_cast<size_t> (ctx->num_cus)*8u;
+    std::vector<double> lines, cubics, profile(1, 0.0);
+    if (!psi_lines(map, lines) || !fpol_lines(field, cubics)) {
+        ctx->fail("a particle source's tables do not fit the host's memory");
+        return nullptr;
+    }
+    if (ns) {
+        profile.assign(sedges, sedges + ns + 1);
+        profile.insert(profile.end(), accept, accept + ns);
+        s->scale = static_cast<double> (ns)/(sedges[ns] - sedges[0]);
+    }
+    if (enter(ctx) ||
+        ctx->check(allocate(s->packed, lines.size()*sizeof(double)), "hipMalloc(flux tables)") ||
+        ctx->check(hipMemcpy(s->packed.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
+        ctx->check(allocate(s->fpol, cubics.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
+        ctx->check(hipMemcpy(s->fpol.get(), cubics.data(), cubics.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)") ||
+        ctx->check(allocate(s->profile, profile.size()*sizeof(double)), "hipMalloc(profile)") ||
+        ctx->check(hipMemcpy(s->profile.get(), profile.data(), profile.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(profile)") ||
+        ctx->check(allocate(s->counters, 4*sizeof(unsigned long long)), "hipMalloc(counters)") ||
+        ctx->check(hipMemsetAsync(s->counters.get(), 0, 4*sizeof(unsigned long long), ctx->stream), "hipMemset(counters)") ||
+        ctx->check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+        return nullptr;
+    }
+    ctx->sources.push_back(std::move(s));
+    return ctx->sources.back().get();
+}
+
+extern "C" void gfhip_source_destroy(gfhip_source *s) {
+    destroy_in(&gfhip_context::sources, s);
+}
+
+extern "C" int gfhip_source_fill(gfhip_source *s, const uint64_t keys[7], uint64_t placed_key, int has_placed,
+                                 uint64_t first_particle, size_t count) {
+    if (!s) return 1;
+    gfhip_context *ctx = s->ctx;
+    if (!keys) return ctx->fail("gfhip_source_fill needs its 7 keys");
+    if (count == 0) return ctx->fail("a particle source fills at least one particle");
+    if (first_particle + static_cast<uint64_t> (count) < first_particle) return ctx->fail("first_particle + count overflows 64 bits");
+    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], placed_key};
+    const size_t used = has_placed ? 8 : 7;
+    const uint32_t dtype = s->is_f32 ? GFIR_F32 : GFIR_F64;
+//  Everything is looked at before anything is allocated.
+    for (size_t c = 0; c < used; c++) {
+        for (size_t other = 0; other < c; other++) {
+            if (all[other] == all[c]) return ctx->fail("a particle source fills eight different buffers: a key is given twice");
+        }
+        const auto found = ctx->buffers.find(all[c]);
+        if (found == ctx->buffers.end()) continue;
+        if (found->second.dtype != dtype) return ctx->fail("a buffer is not of the particle source's type");
+        if (found->second.count < count) return ctx->fail("a particle source's buffer is shorter than the particle count");
+    }
+    if (enter(ctx)) return 1;
+    void *columns[8] = {};
+    for (size_t c = 0; c < used; c++) {
+        if (ensure_buffer(ctx, all[c], count, dtype, nullptr)) return 1;
+        columns[c] = find_buffer(ctx, all[c])->pointer;
+    }
+    gfhip::launch_particle_source(columns, columns[7], s->is_f32, count, first_particle, s->map, s->field, s->par, s->packed.get(),
+                                  s->fpol.get(), s->profile.get(), s->scale, s->refill, s->max_workgroups, s->counters.get(),
+                                  ctx->stream);
+    return ctx->check(hipGetLastError(), "particle source launch");
+}
+
+extern "C" int gfhip_source_counts(gfhip_source *s, uint64_t counters[4]) {
+    if (!s) return 1;
+    gfhip_context *ctx = s->ctx;
+    if (!counters) return ctx->fail("gfhip_source_counts needs a destination");
+    if (enter(ctx)) return 1;
+    unsigned long long host[4] = {0, 0, 0, 0};
+    GFHIP_TRY(ctx, hipMemcpyAsync(host, s->counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
+    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int k = 0; k < 4; k++) counters[k] = host[k];
+    return 0;
+}
+
+//  Not through enter(): as gfhip_flux_info.
+extern "C" int gfhip_source_info(gfhip_source *s, struct gfhip_flux_info *info) {
+    if (!s) return 1;
+    if (!info) return s->ctx->fail("gfhip_source_info needs a destination");
+    info->private_sums = s->refill ? 1u : 0u;
+    info->workgroup_size = 256;
+    info->cap_cells = 0;
+    info->max_workgroups = s->max_workgroups;
+    info->lds_bytes = s->par.ns ? (2*static_cast<size_t> (s->par.ns) + 1)*sizeof(double) : 0;
+    return 0;
+}
+
+extern "C" int gfhip_source_fill_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double box[4], double slo,
+                                      double shi, double blo, double bhi, double xlo, double xhi, const double *sedges,
+                                      const double *accept, size_t ns, uint64_t seed, uint32_t attempts, uint32_t flags,
+                                      void *const columns[8], int is_f32, uint64_t first_particle, size_t count,
+                                      uint64_t counters[4]) {
+    bool complete = map && field && columns && counters;
+    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
+    if (!complete) {
+        creation_error = "gfhip_source_fill_host needs a map, a field, the seven columns and the counters";
+        return 1;
+    }
+    gfhip::flux::map m;
+    gfhip::flux::field f;
+    gfhip::draw::parameters par;
+    const char *refused = flux_map_of(map, m);
+    if (!refused) refused = phase_field_of(field, f);
+    if (!refused) refused = source_parameters_of(box, slo, shi, blo, bhi, xlo, xhi, sedges, accept, ns, seed, attempts, flags, par);
+    if (!refused && first_particle + static_cast<uint64_t> (count) < first_particle) refused = "first_particle + count overflows 64 bits";
+    if (refused) {
+        creation_error = refused;
+        return 1;
+    }
+    const gfhip::draw::host_tables tables = {map->coefficients, static_cast<size_t> (map->numr*map->numz),
+                                             {field->fpol[0], field->fpol[1], field->fpol[2], field->fpol[3]}, sedges, accept, ns};
+    if (is_f32) {
+        gfhip::draw::fill_host<float> (m, f, par, tables, columns, columns[7], first_particle, count, counters);
+    } else {
+        gfhip::draw::fill_host<double> (m, f, par, tables, columns, columns[7], first_particle, count, counters);
+    }
+    return 0;
+}
+
+extern "C" void gfhip_source_block_host(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
+    gfhip::draw::philox(counter, key, out);
 }
 
 //  What a run of quadrature points needs beside the map (flux_label.hpp), or why it is refused.

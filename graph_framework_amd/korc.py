@@ -20,6 +20,11 @@ _NP = {"f64": np.float64, "f32": np.float32}
 ITEMS = ("korc_axis_newton", "korc_bmod_at_axis", "korc_initialize_gamma", "korc_step")
 
 
+def blank(count):
+    """The seven zero columns to construct a Korc of `count` particles from, for Korc.load to fill."""
+    return {k: np.zeros(int(count)) for k in PARTICLE}
+
+
 def _item(items, name, dtype):
     """GFIR bytes received from rank 0 (`items`), else the exported workload file."""
     return items[name] if items and name in items else workload(name, dtype)
@@ -82,12 +87,29 @@ class Korc:
         self.step_item = self.work.add_item(_item(items, "korc_step", dtype), list(PARTICLE), [],
                                             self.num_particles, self.host)
         self.steps_done = 0                                  # steps run so far: the step number of track()
+        self.compiled = self.pre_ran = False                 # load() belongs between the two
 
     def compile(self):
         self.work.compile()
+        self.compiled = True
 
     def pre_run(self):
         self.work.pre_run()
+        self.pre_ran = True
+
+    def load(self, source, placed=None):
+        """Fill the push's seven buffers where they lie on the device (the tensors of device_state included) from a
+        source.ParticleSource made on self.work.context for the push's dtype: particles self.first_particle .. of the
+        ensemble, enqueued on the push's stream, no copy.  placed: the key of a buffer that receives 1 for a placed
+        particle and 0 for an unplaced one (NaN in all seven columns), a weight for bin() and track().  Between compile(),
+        which creates the buffers, and pre_run(), which makes gamma and gamma*beta of the loaded beta."""
+        if source.context is not self.work.context:
+            raise ValueError("the source must be created on the push's context (push.work.context)")
+        if source.dtype != np.dtype(self.np_dtype):
+            raise ValueError("the source fills %s columns, the push has %s" % (source.dtype.name, np.dtype(self.np_dtype).name))
+        if not self.compiled or self.pre_ran:
+            raise RuntimeError("load() belongs after compile() and before pre_run()")
+        source.fill(*PARTICLE, self.num_particles, self.first_particle, placed=placed)
 
     def run(self, steps=1):
         self.work.run(steps)

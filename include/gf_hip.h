@@ -722,6 +722,61 @@ int gfhip_moments_add_particles_host(const struct gfhip_flux_map *map, const str
                                      const double *sedges, size_t ns, size_t batches, const void *const columns[8], int is_f32,
                                      size_t count, uint64_t first_particle, int64_t *limbs, uint64_t counters[3]);
 
+/* A particle source: the seven columns of a push filled where they lie on the device, from a stated distribution
+ * (csrc/particle_source.hip).  Particle p, its index in the WHOLE ensemble, is drawn from Philox4x32-10 with counter
+ * (lo32(p), hi32(p), attempt, purpose) and key (lo32(seed), hi32(seed)), in the fixed fp64 arithmetic of
+ * csrc/particle_draw.hpp, which states every line: p is the same particle, to the last bit, on any device, for any split
+ * into shards, launch shape or route, and on the host.
+ *     position   uniform in volume in the box rlo <= R < rhi, zlo <= z < zhi (R*R uniform, the toroidal angle uniform),
+ *                rounded to the columns' type, kept iff slo <= label < shi for the label of the STORED position (a NaN or
+ *                a point off the map is not), and with a profile iff also u < accept[is], `is` the cell of the label
+ *                among sedges (in no cell: not kept); up to `attempts` candidates
+ *     momentum   components of beta = v/c: |beta| uniform in [blo, bhi), the pitch cosine to the local field
+ *                B = (psi_z, fpol, -psi_R)/R uniform in [xlo, xhi), the gyrophase uniform; gamma = 0.  The push's own
+ *                initialize_gamma makes gamma and gamma*beta of them.
+ * A particle that runs out of attempts, or sits where the field has no direction, is UNPLACED: the quiet NaN without
+ * payload in all seven columns.  `placed`, a column of the same type, receives 1 or 0: a weight for every other entry
+ * point.  The four counters: placed, unplaced, position_tries (the candidates examined, summed over the particles) and
+ * gyro_tries.
+ *
+ * gfhip_source_create: box = {rlo, rhi, zlo, zhi}; sedges (ns + 1) and accept (ns) both NULL with ns = 0: no profile;
+ *   fp32 columns when is_f32 is non-zero; flags: GFHIP_SOURCE_PLAIN (one lane, one particle) or GFHIP_SOURCE_REFILL (a
+ *   lane that has settled its particle takes its wave's next one), neither: the library's choice, the same bytes either
+ *   way; max_workgroups: 0 for the launch rule of the global deposits.  Refused: what gfhip_phase_create refuses for
+ *   the map and the field; a box, label range, speed range or pitch range that is empty or has a NaN or an infinity;
+ *   rlo < 0; blo < 0 or bhi >= 1; xlo < -1 or xhi > 1; attempts = 0 or > 4096; ns > 256, edges that are not finite and
+ *   strictly increasing, accept outside [0, 1] or NaN, one of sedges and accept without the other; unknown flags or both
+ *   routes.
+ * gfhip_source_fill: particles first_particle .. first_particle + count into elements 0 .. count of the seven buffers
+ *   (and of placed_key when has_placed is non-zero), which are allocated by gfhip_allocate_buffer's rule where absent.
+ *   Asynchronous on the context's stream.  Refused before any launch, with nothing changed or allocated: count = 0,
+ *   first_particle + count beyond 64 bits, an existing buffer of another type than the source's or shorter than
+ *   `count`, the same key twice.
+ * gfhip_source_counts: the four counters of all fills so far, after the stream has drained.
+ * gfhip_source_info: private_sums 1 for the refill route, workgroup_size, max_workgroups and lds_bytes of a launch.
+ * gfhip_source_fill_host: no device, no context; the same lines on the CPU (csrc/source_host.hpp) into the caller's
+ *   arrays, columns[0..6] and columns[7] = placed or NULL, float when is_f32 is non-zero and double otherwise;
+ *   counters[4] are added to.  flags are checked and otherwise without effect.  Errors: gfhip_last_error(NULL).
+ * gfhip_source_block_host: one Philox4x32-10 block. */
+#define GFHIP_SOURCE_PLAIN 1u
+#define GFHIP_SOURCE_REFILL 2u
+typedef struct gfhip_source gfhip_source;
+
+gfhip_source *gfhip_source_create(gfhip_context *ctx, const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field,
+                                  const double box[4], double slo, double shi, double blo, double bhi, double xlo, double xhi,
+                                  const double *sedges, const double *accept, size_t ns, uint64_t seed, uint32_t attempts,
+                                  int is_f32, uint32_t flags, size_t max_workgroups);
+int gfhip_source_fill(gfhip_source *source, const uint64_t keys[7], uint64_t placed_key, int has_placed, uint64_t first_particle,
+                      size_t count);
+int gfhip_source_counts(gfhip_source *source, uint64_t counters[4]);
+int gfhip_source_info(gfhip_source *source, struct gfhip_flux_info *info);
+void gfhip_source_destroy(gfhip_source *source);
+int gfhip_source_fill_host(const struct gfhip_flux_map *map, const struct gfhip_spectrum_field *field, const double box[4],
+                           double slo, double shi, double blo, double bhi, double xlo, double xhi, const double *sedges,
+                           const double *accept, size_t ns, uint64_t seed, uint32_t attempts, uint32_t flags,
+                           void *const columns[8], int is_f32, uint64_t first_particle, size_t count, uint64_t counters[4]);
+void gfhip_source_block_host(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+
 /* Host side, no device: the correctly rounded sum of `count` finite doubles through the same
  * superaccumulator functions the kernels run; `limbs` (67 words, or NULL) receives the canonical state.
  * Non-zero for a NaN or an infinity among the values (gfhip_last_error(NULL)). */
