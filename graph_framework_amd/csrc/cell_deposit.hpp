@@ -1,9 +1,10 @@
 //------------------------------------------------------------------------------
 ///  @file cell_deposit.hpp
-///  @brief The pieces of a deposit that deposition.hip and flux_profile.hip share (device side).
+///  @brief The pieces of a deposit that every deposit kernel shares (device side): deposition.hip and, through
+///  flux_sums.hpp, flux_profile.hip, flux_spectrum.hip, phase_bins.hip, moment_bins.hip and confinement.hip.
 ///
 ///  A store of exact sums is cells x 67 limbs of superacc.hpp, [cell][limb], and three counters (samples, outside,
-///  skipped).  The two deposit kernels differ in how a sample finds its cell and in where the limbs live (global
+///  skipped).  The deposit kernels differ in how a sample finds its cell and in where the limbs live (global
 ///  memory, or a workgroup's LDS); what a sample adds, how the counters are kept and how the limbs are added to is
 ///  written here, once.
 //------------------------------------------------------------------------------

@@ -112,53 +112,32 @@ confinement_reset_kernel(const unsigned long long count, unsigned int *__restric
     }
 }
 
-namespace {
-
-template<typename T>
-void check_as(const void *const *columns, void *alive, const size_t first, const size_t count, const flux::map &m,
-              const double *packed, const double limit, const double *edges, const size_t *n, const double *scale,
-              const uint32_t step, uint32_t *lost_step, double *exit_r, double *exit_z, unsigned long long *newly_lost,
-              const unsigned int block, const size_t max_workgroups, const size_t lds_bytes, void *state,
-              unsigned long long *counters, hipStream_t stream) {
-    const T *const *typed = reinterpret_cast<const T *const *> (columns);
-    const confine_columns<T> in = {typed[0] + first, typed[1] + first, typed[2] + first, typed[6] + first,
-                                   typed[7] ? typed[7] + first : nullptr, static_cast<T *> (alive) + first};
-    hipLaunchKernelGGL(confinement_check_kernel<T>, dim3(grid_of(count, block, max_workgroups)), dim3(block), lds_bytes, stream,
-                       in, static_cast<unsigned long long> (count), m, packed, limit, edges, static_cast<int> (n[0]),
-                       static_cast<int> (n[1]), static_cast<int> (n[2]), scale[0], scale[1], scale[2], step, lost_step + first,
-                       exit_r ? exit_r + first : nullptr, exit_z ? exit_z + first : nullptr, newly_lost,
-                       static_cast<unsigned long long *> (state), counters);
-}
-
-}  // namespace
-
 void launch_confinement_check(const void *const *columns, void *alive, const bool is_f32, const size_t first, const size_t count,
-                              const flux::map &m, const double *packed, const double limit, const double *edges,
-                              const size_t *n, const double *scale, const uint32_t step, uint32_t *lost_step, double *exit_r,
-                              double *exit_z, unsigned long long *newly_lost, const unsigned int block,
-                              const size_t max_workgroups, const size_t lds_bytes, void *state, unsigned long long *counters,
-                              hipStream_t stream) {
+                              const cell_tables &t, const double limit, const double *edges, const size_t *n,
+                              const double *scale, const uint32_t step, uint32_t *lost_step, double *exit_r, double *exit_z,
+                              unsigned long long *newly_lost, const launch_shape &shape, const cell_target &to) {
     if (count == 0) return;
-    if (is_f32) {
-        check_as<float> (columns, alive, first, count, m, packed, limit, edges, n, scale, step, lost_step, exit_r, exit_z,
-                         newly_lost, block, max_workgroups, lds_bytes, state, counters, stream);
-    } else {
-        check_as<double> (columns, alive, first, count, m, packed, limit, edges, n, scale, step, lost_step, exit_r, exit_z,
-                          newly_lost, block, max_workgroups, lds_bytes, state, counters, stream);
-    }
+    with_particle_type(is_f32, [&](auto type) {
+        using T = decltype(type);
+        const T *const *typed = reinterpret_cast<const T *const *> (columns);
+        const confine_columns<T> in = {typed[0] + first, typed[1] + first, typed[2] + first, typed[6] + first,
+                                       typed[7] ? typed[7] + first : nullptr, static_cast<T *> (alive) + first};
+        hipLaunchKernelGGL(confinement_check_kernel<T>, dim3(grid_of(count, shape.block, shape.max_workgroups)), dim3(shape.block),
+                           shape.lds_bytes, to.stream, in, static_cast<unsigned long long> (count), t.map, t.packed, limit, edges,
+                           static_cast<int> (n[0]), static_cast<int> (n[1]), static_cast<int> (n[2]), scale[0], scale[1], scale[2],
+                           step, lost_step + first, exit_r ? exit_r + first : nullptr, exit_z ? exit_z + first : nullptr,
+                           newly_lost, static_cast<unsigned long long *> (to.state), to.counters);
+    });
 }
 
 void launch_confinement_reset(const size_t count, uint32_t *lost_step, void *alive, const bool is_f32, double *exit_r,
                               double *exit_z, hipStream_t stream) {
     if (count == 0) return;
-    const dim3 grid(static_cast<unsigned int> ((count + 255)/256));
-    if (is_f32) {
-        hipLaunchKernelGGL(confinement_reset_kernel<float>, grid, dim3(256), 0, stream, static_cast<unsigned long long> (count),
-                           lost_step, static_cast<float *> (alive), exit_r, exit_z);
-    } else {
-        hipLaunchKernelGGL(confinement_reset_kernel<double>, grid, dim3(256), 0, stream, static_cast<unsigned long long> (count),
-                           lost_step, static_cast<double *> (alive), exit_r, exit_z);
-    }
+    with_particle_type(is_f32, [&](auto type) {
+        using T = decltype(type);
+        hipLaunchKernelGGL(confinement_reset_kernel<T>, dim3(static_cast<unsigned int> ((count + 255)/256)), dim3(256), 0, stream,
+                           static_cast<unsigned long long> (count), lost_step, static_cast<T *> (alive), exit_r, exit_z);
+    });
 }
 
 }  // namespace gfhip

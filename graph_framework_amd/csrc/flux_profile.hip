@@ -153,97 +153,65 @@ flux_label_kernel(const double *__restrict__ x, const double *__restrict__ y, co
 //  The shape of the deposit launches of a profile (cells + 1 edges) or a spectrum (its two axes' edges).  The private
 //  path is taken when the grid and the edges fit the LDS of one workgroup and the caller has not switched it off; `cap`
 //  is the most cells it takes.
-void flux_launch_shape(const size_t cells, const size_t edge_count, const bool allow_private, const unsigned int num_cus,
-                       bool *is_private, size_t *cap, unsigned int *block, size_t *max_workgroups, size_t *lds_bytes) {
-    *cap = private_cap;
+launch_shape flux_launch_shape(const size_t cells, const size_t edge_count, const bool allow_private, const unsigned int num_cus) {
+    launch_shape shape = {};
+    shape.cap = private_cap;
     const size_t edge_bytes = edge_count*sizeof(double);
-    *is_private = allow_private && cells <= *cap && cells*bytes_per_cell + edge_bytes <= lds_per_workgroup;
-    if (*is_private) {
-        *lds_bytes = cells*bytes_per_cell + edge_bytes;
-        *block = private_block;
+    shape.is_private = allow_private && cells <= shape.cap && cells*bytes_per_cell + edge_bytes <= lds_per_workgroup;
+    if (shape.is_private) {
+        shape.lds_bytes = cells*bytes_per_cell + edge_bytes;
+        shape.block = private_block;
 //  Two workgroups of 1024 are all the waves a CU holds; large grids leave room for one.
-        const size_t per_cu = lds_per_workgroup/(*lds_bytes) >= 2 ? 2 : 1;
-        *max_workgroups = static_cast<size_t> (num_cus)*per_cu;
+        const size_t per_cu = lds_per_workgroup/shape.lds_bytes >= 2 ? 2 : 1;
+        shape.max_workgroups = static_cast<size_t> (num_cus)*per_cu;
     } else {
-        *lds_bytes = edge_bytes;
-        *block = global_block;
-        *max_workgroups = static_cast<size_t> (num_cus)*8u;
+        shape.lds_bytes = edge_bytes;
+        shape.block = global_block;
+        shape.max_workgroups = static_cast<size_t> (num_cus)*8u;
     }
+    return shape;
 }
 
-//  Dynamic LDS above 64 KiB has to be asked for.  The setting belongs to the function on the current device, not to a
-//  profile: always the cap's size, so that no profile lowers what another one needs.
 hipError_t flux_prepare() {
-    for (const void *kernel : {reinterpret_cast<const void *> (&flux_deposit_kernel<true>),
-                               reinterpret_cast<const void *> (&flux_deposit_rays_kernel<true>),
-                               reinterpret_cast<const void *> (&flux_volume_kernel<true>)}) {
-        const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      static_cast<int> (private_cap_bytes));
-        if (status != hipSuccess) return status;
-    }
-    return hipSuccess;
+    return prepare_private({reinterpret_cast<const void *> (&flux_deposit_kernel<true>),
+                            reinterpret_cast<const void *> (&flux_deposit_rays_kernel<true>),
+                            reinterpret_cast<const void *> (&flux_volume_kernel<true>)}, private_cap_bytes);
 }
 
 void launch_flux_deposit(const double *x, const double *y, const double *z, const double *value, const size_t count,
-                         const flux::map &m, const double *packed, const double *edges, const size_t cells, const double scale,
-                         const bool is_private, const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
-                         void *state, unsigned long long *counters, hipStream_t stream) {
+                         const cell_tables &t, const double *edges, const size_t cells, const double scale,
+                         const launch_shape &shape, const cell_target &to) {
     if (count == 0) return;
-    const size_t want = (count + block - 1)/block;
-    const unsigned int grid = static_cast<unsigned int> (want < max_workgroups ? want : max_workgroups);
-    if (is_private) {
-        hipLaunchKernelGGL(flux_deposit_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
-                           static_cast<unsigned long long> (count), m, packed, edges, static_cast<int> (cells), scale,
-                           static_cast<unsigned long long *> (state), counters);
-    } else {
-        hipLaunchKernelGGL(flux_deposit_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
-                           static_cast<unsigned long long> (count), m, packed, edges, static_cast<int> (cells), scale,
-                           static_cast<unsigned long long *> (state), counters);
-    }
+    launch_on_route(flux_deposit_kernel<true>, flux_deposit_kernel<false>, shape, grid_of(count, shape.block, shape.max_workgroups),
+                    to.stream, x, y, z, value, static_cast<unsigned long long> (count), t.map, t.packed, edges,
+                    static_cast<int> (cells), scale, static_cast<unsigned long long *> (to.state), to.counters);
 }
 
 void launch_flux_deposit_rays(const double *x, const double *y, const double *z, const double *value, const size_t count,
-                              const unsigned long long first_ray, const size_t batch_count, const flux::map &m,
-                              const double *packed, const double *edges, const size_t cells, const double scale,
-                              const bool is_private, const unsigned int block, const size_t max_workgroups,
-                              const size_t lds_bytes, void *state, unsigned long long *counters, hipStream_t stream) {
+                              const unsigned long long first_ray, const size_t batch_count, const cell_tables &t,
+                              const double *edges, const size_t cells, const double scale, const launch_shape &shape,
+                              const cell_target &to) {
     if (count == 0) return;
-    const unsigned int grid = batched_grid_of(count, block, max_workgroups, batch_count);
-    if (is_private) {
-        hipLaunchKernelGGL(flux_deposit_rays_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
-                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, packed,
-                           edges, static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
-    } else {
-        hipLaunchKernelGGL(flux_deposit_rays_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, x, y, z, value,
-                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, packed,
-                           edges, static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
-    }
+    launch_on_route(flux_deposit_rays_kernel<true>, flux_deposit_rays_kernel<false>, shape,
+                    batched_grid_of(count, shape.block, shape.max_workgroups, batch_count), to.stream, x, y, z, value,
+                    static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), t.map, t.packed,
+                    edges, static_cast<int> (cells), scale, static_cast<unsigned long long *> (to.state), to.counters);
 }
 
 void launch_flux_volumes(const unsigned long long first, const size_t count, const unsigned long long row, const double twice_sub,
-                         const double area, const flux::window &window, const flux::map &m, const double *packed,
-                         const double *edges, const size_t cells, const double scale, const bool is_private,
-                         const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
-                         void *state, unsigned long long *counters, hipStream_t stream) {
+                         const double area, const flux::window &window, const cell_tables &t, const double *edges,
+                         const size_t cells, const double scale, const launch_shape &shape, const cell_target &to) {
     if (count == 0) return;
-    const size_t want = (count + block - 1)/block;
-    const unsigned int grid = static_cast<unsigned int> (want < max_workgroups ? want : max_workgroups);
-    if (is_private) {
-        hipLaunchKernelGGL(flux_volume_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, first,
-                           static_cast<unsigned long long> (count), row, twice_sub, area, window, m, packed, edges,
-                           static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
-    } else {
-        hipLaunchKernelGGL(flux_volume_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, first,
-                           static_cast<unsigned long long> (count), row, twice_sub, area, window, m, packed, edges,
-                           static_cast<int> (cells), scale, static_cast<unsigned long long *> (state), counters);
-    }
+    launch_on_route(flux_volume_kernel<true>, flux_volume_kernel<false>, shape, grid_of(count, shape.block, shape.max_workgroups),
+                    to.stream, first, static_cast<unsigned long long> (count), row, twice_sub, area, window, t.map, t.packed,
+                    edges, static_cast<int> (cells), scale, static_cast<unsigned long long *> (to.state), to.counters);
 }
 
-void launch_flux_label(const double *x, const double *y, const double *z, const size_t count, const flux::map &m,
-                       const double *packed, double *label, hipStream_t stream) {
+void launch_flux_label(const double *x, const double *y, const double *z, const size_t count, const cell_tables &t,
+                       double *label, hipStream_t stream) {
     if (count == 0) return;
     hipLaunchKernelGGL(flux_label_kernel, dim3(static_cast<unsigned int> ((count + 255)/256)), dim3(256), 0, stream, x, y, z,
-                       static_cast<unsigned long long> (count), m, packed, label);
+                       static_cast<unsigned long long> (count), t.map, t.packed, label);
 }
 
 }  // namespace gfhip

@@ -35,26 +35,17 @@ namespace {
 constexpr size_t private_cap_bytes = private_cap*bytes_per_cell + (private_cap + 3)*sizeof(double);
 static_assert(private_cap_bytes <= lds_per_workgroup, "the cap fits one workgroup's LDS");
 
-//  The label and N of one sample, both NaN outside the map.  `fpol`: [interval][4], 32-byte aligned.
+//  The label and N of one sample, both NaN outside the map.
 __device__ __forceinline__ double npar_at(const flux::map &m, const flux::field &f, const double *__restrict__ packed,
                                           const double *__restrict__ fpol, const double x, const double y, const double z,
                                           const double kx, const double ky, const double kz, const double w, double &label) {
-    double tr, tz;
-    const long long at = flux::locate(m, x, y, z, tr, tz);
-    if (at < 0) {
+    field_point p;
+    if (!point_at(m, f, packed, fpol, x, y, z, p)) {
         label = __builtin_nan("");
         return __builtin_nan("");
     }
-    double c[16];
-    coefficients_at(packed, at, c);
-    double gr, gz, tp;
-    const double psi = flux::psi_gradient(m, c, tr, tz, gr, gz);
-    label = flux::canonical(flux::label_of(m, psi));
-    const int q = flux::fpol_interval(f, psi, tp);
-    const double2 *line = reinterpret_cast<const double2 *> (fpol) + static_cast<size_t> (q)*2;
-    const double2 low = line[0], high = line[1];
-    const double cubic[4] = {low.x, low.y, high.x, high.y};
-    return flux::npar_of(f, x, y, flux::radius_of(x, y), kx, ky, kz, w, gr, gz, flux::fpol_of(cubic, tp));
+    label = p.label;
+    return flux::npar_of(f, x, y, flux::radius_of(x, y), kx, ky, kz, w, p.gr, p.gz, p.fpol);
 }
 
 }  // namespace
@@ -140,66 +131,49 @@ spectrum_npar_kernel(const spectrum_columns in, const unsigned long long count, 
     }
 }
 
-//  Dynamic LDS above 64 KiB has to be asked for: always the cap's size, as flux_prepare does.
 hipError_t spectrum_prepare() {
-    for (const void *kernel : {reinterpret_cast<const void *> (&spectrum_deposit_kernel<true>),
-                               reinterpret_cast<const void *> (&spectrum_deposit_rays_kernel<true>)}) {
-        const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      static_cast<int> (private_cap_bytes));
-        if (status != hipSuccess) return status;
-    }
-    return hipSuccess;
+    return prepare_private({reinterpret_cast<const void *> (&spectrum_deposit_kernel<true>),
+                            reinterpret_cast<const void *> (&spectrum_deposit_rays_kernel<true>)}, private_cap_bytes);
 }
 
-void launch_spectrum_deposit(const double *const *columns, const size_t first, const size_t count, const flux::map &m,
-                             const flux::field &f, const double *packed, const double *fpol, const double *edges,
-                             const size_t ns, const size_t nn, const double sscale, const double nscale, const bool is_private,
-                             const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
-                             void *state, unsigned long long *counters, hipStream_t stream) {
+namespace {
+
+//  The first `used` columns from sample `first` on.
+spectrum_columns columns_at(const double *const *columns, const size_t first, const bool with_value) {
+    return {columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, columns[4] + first,
+            columns[5] + first, columns[6] + first, with_value ? columns[7] + first : nullptr};
+}
+
+}  // namespace
+
+void launch_spectrum_deposit(const double *const *columns, const size_t first, const size_t count, const cell_tables &t,
+                             const double *edges, const size_t *n, const double *scale, const launch_shape &shape,
+                             const cell_target &to) {
     if (count == 0) return;
-    const spectrum_columns in = {columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first,
-                                 columns[4] + first, columns[5] + first, columns[6] + first, columns[7] + first};
-    const unsigned int grid = grid_of(count, block, max_workgroups);
-    if (is_private) {
-        hipLaunchKernelGGL(spectrum_deposit_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), m, f, packed, fpol, edges, static_cast<int> (ns),
-                           static_cast<int> (nn), sscale, nscale, static_cast<unsigned long long *> (state), counters);
-    } else {
-        hipLaunchKernelGGL(spectrum_deposit_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), m, f, packed, fpol, edges, static_cast<int> (ns),
-                           static_cast<int> (nn), sscale, nscale, static_cast<unsigned long long *> (state), counters);
-    }
+    launch_on_route(spectrum_deposit_kernel<true>, spectrum_deposit_kernel<false>, shape,
+                    grid_of(count, shape.block, shape.max_workgroups), to.stream, columns_at(columns, first, true),
+                    static_cast<unsigned long long> (count), t.map, t.field, t.packed, t.fpol, edges, static_cast<int> (n[0]),
+                    static_cast<int> (n[1]), scale[0], scale[1], static_cast<unsigned long long *> (to.state), to.counters);
 }
 
 void launch_spectrum_deposit_rays(const double *const *columns, const size_t first, const size_t count,
-                                  const unsigned long long first_ray, const size_t batch_count, const flux::map &m,
-                                  const flux::field &f, const double *packed, const double *fpol, const double *edges,
-                                  const size_t ns, const size_t nn, const double sscale, const double nscale,
-                                  const bool is_private, const unsigned int block, const size_t max_workgroups,
-                                  const size_t lds_bytes, void *state, unsigned long long *counters, hipStream_t stream) {
+                                  const unsigned long long first_ray, const size_t batch_count, const cell_tables &t,
+                                  const double *edges, const size_t *n, const double *scale, const launch_shape &shape,
+                                  const cell_target &to) {
     if (count == 0) return;
-    const spectrum_columns in = {columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first,
-                                 columns[4] + first, columns[5] + first, columns[6] + first, columns[7] + first};
-    const unsigned int grid = batched_grid_of(count, block, max_workgroups, batch_count);
-    if (is_private) {
-        hipLaunchKernelGGL(spectrum_deposit_rays_kernel<true>, dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, f,
-                           packed, fpol, edges, static_cast<int> (ns), static_cast<int> (nn), sscale, nscale,
-                           static_cast<unsigned long long *> (state), counters);
-    } else {
-        hipLaunchKernelGGL(spectrum_deposit_rays_kernel<false>, dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), first_ray, static_cast<unsigned int> (batch_count), m, f,
-                           packed, fpol, edges, static_cast<int> (ns), static_cast<int> (nn), sscale, nscale,
-                           static_cast<unsigned long long *> (state), counters);
-    }
+    launch_on_route(spectrum_deposit_rays_kernel<true>, spectrum_deposit_rays_kernel<false>, shape,
+                    batched_grid_of(count, shape.block, shape.max_workgroups, batch_count), to.stream,
+                    columns_at(columns, first, true), static_cast<unsigned long long> (count), first_ray,
+                    static_cast<unsigned int> (batch_count), t.map, t.field, t.packed, t.fpol, edges, static_cast<int> (n[0]),
+                    static_cast<int> (n[1]), scale[0], scale[1], static_cast<unsigned long long *> (to.state), to.counters);
 }
 
-void launch_spectrum_npar(const double *const *columns, const size_t count, const flux::map &m, const flux::field &f,
-                          const double *packed, const double *fpol, double *label, double *npar, hipStream_t stream) {
+void launch_spectrum_npar(const double *const *columns, const size_t count, const cell_tables &t, double *label, double *npar,
+                          hipStream_t stream) {
     if (count == 0) return;
-    const spectrum_columns in = {columns[0], columns[1], columns[2], columns[3], columns[4], columns[5], columns[6], nullptr};
-    hipLaunchKernelGGL(spectrum_npar_kernel, dim3(static_cast<unsigned int> ((count + 255)/256)), dim3(256), 0, stream, in,
-                       static_cast<unsigned long long> (count), m, f, packed, fpol, label, npar);
+    hipLaunchKernelGGL(spectrum_npar_kernel, dim3(static_cast<unsigned int> ((count + 255)/256)), dim3(256), 0, stream,
+                       columns_at(columns, 0, false), static_cast<unsigned long long> (count), t.map, t.field, t.packed, t.fpol,
+                       label, npar);
 }
 
 }  // namespace gfhip

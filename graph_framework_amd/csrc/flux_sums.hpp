@@ -1,9 +1,12 @@
 //------------------------------------------------------------------------------
 ///  @file flux_sums.hpp
-///  @brief What the deposit kernels of flux_profile.hip, flux_spectrum.hip, phase_bins.hip and moment_bins.hip share
-///  (device side): the label of a point from the repacked psi tables, a workgroup's sums, private in LDS or global, and
-///  the deposit of the batched variants, one batch of rays or particles (ray_batches.hpp) at a time, with one value per
-///  sample or several.
+///  @brief What the deposit kernels of flux_profile.hip, flux_spectrum.hip, phase_bins.hip, moment_bins.hip and
+///  confinement.hip share.  Device side: the label of a point from the repacked psi tables and the point with its field
+///  (point_at), a workgroup's sums, private in LDS or global, and the deposit of the batched variants, one batch of rays
+///  or particles (ray_batches.hpp) at a time, with one value per sample or several.  The plain kernels keep their
+///  grid-stride loop written out: behind a shared loop function they need more registers or run slower (DESIGN.md
+///  section 19).  Launch side: the particles' columns, the grid of a launch and the helpers that choose a kernel's route
+///  and type.
 //------------------------------------------------------------------------------
 #ifndef GFHIP_FLUX_SUMS_HPP
 #define GFHIP_FLUX_SUMS_HPP
@@ -11,7 +14,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "cell_deposit.hpp"
+#include "cell_launch.hpp"
 #include "flux_label.hpp"
 #include "ray_batches.hpp"
 #include "superacc.hpp"
@@ -45,6 +51,33 @@ __device__ __forceinline__ double label_at(const flux::map &m, const double *__r
     double c[16];
     coefficients_at(packed, at, c);
     return flux::label_of(m, flux::psi_of(c, tr, tz));
+}
+
+//  A point inside the map as the spectrum, the distribution and the moments need it: psi, its derivatives along R and
+//  z, the canonical label and fpol.
+struct field_point {
+    double psi, gr, gz, label, fpol;
+};
+
+//  The field_point of (x, y, z), or false outside the map (`p` is then left alone).  `fpol`: [interval][4], 32-byte
+//  aligned.  Only calls of flux_label.hpp's functions: no arithmetic of its own.
+__device__ __forceinline__ bool point_at(const flux::map &m, const flux::field &f, const double *__restrict__ packed,
+                                         const double *__restrict__ fpol, const double x, const double y, const double z,
+                                         field_point &p) {
+    double tr, tz;
+    const long long at = flux::locate(m, x, y, z, tr, tz);
+    if (at < 0) return false;
+    double c[16];
+    coefficients_at(packed, at, c);
+    double tp;
+    p.psi = flux::psi_gradient(m, c, tr, tz, p.gr, p.gz);
+    const int q = flux::fpol_interval(f, p.psi, tp);
+    const double2 *line = reinterpret_cast<const double2 *> (fpol) + static_cast<size_t> (q)*2;
+    const double2 low = line[0], high = line[1];
+    const double cubic[4] = {low.x, low.y, high.x, high.y};
+    p.fpol = flux::fpol_of(cubic, tp);
+    p.label = flux::canonical(flux::label_of(m, p.psi));
+    return true;
 }
 
 //  What the deposit kernels share.  PRIVATE: dynamic LDS = cells*67 limbs, then the staged edges; else the edges
@@ -177,6 +210,24 @@ __device__ __forceinline__ void deposit_batched_many(const workgroup_sums<PRIVAT
     deposit::flush(tally, counters);
 }
 
+//  A particle's columns as the push holds them, all of T; weight: null when every particle has weight 1.0.
+template<typename T>
+struct particle_columns {
+    const T *x, *y, *z, *ux, *uy, *uz, *gamma, *weight;
+
+    __device__ __forceinline__ double weight_of(const unsigned long long at) const {
+        return weight ? static_cast<double> (weight[at]) : 1.0;
+    }
+};
+
+//  Those of a launch that begins at particle `first` of the caller's eight (the eighth null without weights).
+template<typename T>
+particle_columns<T> columns_from(const void *const *columns, const size_t first, const bool with_weight) {
+    const T *const *typed = reinterpret_cast<const T *const *> (columns);
+    return {typed[0] + first, typed[1] + first, typed[2] + first, typed[3] + first, typed[4] + first, typed[5] + first,
+            typed[6] + first, with_weight ? typed[7] + first : nullptr};
+}
+
 //  The workgroups of a launch of `count` samples.
 inline unsigned int grid_of(const size_t count, const unsigned int block, const size_t max_workgroups) {
     const size_t want = (count + block - 1)/block;
@@ -186,6 +237,34 @@ inline unsigned int grid_of(const size_t count, const unsigned int block, const 
 //  Those of a batched launch: with more than one per batch, a whole number per batch (ray_batches.hpp).
 inline unsigned int batched_grid_of(const size_t count, const unsigned int block, const size_t max_workgroups, const size_t batch_count) {
     return batches::whole_teams(grid_of(count, block, max_workgroups), static_cast<unsigned int> (batch_count));
+}
+
+//  A deposit launch on the route the shape was decided for: the kernel's <true> or its <false>.
+template<typename... PARAMETERS, typename... ARGUMENTS>
+void launch_on_route(void (*private_kernel)(PARAMETERS...), void (*global_kernel)(PARAMETERS...), const launch_shape &shape,
+                     const unsigned int grid, hipStream_t stream, ARGUMENTS... arguments) {
+    hipLaunchKernelGGL(shape.is_private ? private_kernel : global_kernel, dim3(grid), dim3(shape.block), shape.lds_bytes,
+                       stream, arguments...);
+}
+
+//  with(float()) or with(double()): the particles' type, chosen once per launch.
+template<typename WITH>
+void with_particle_type(const bool is_f32, WITH with) {
+    if (is_f32) {
+        with(float());
+    } else {
+        with(double());
+    }
+}
+
+//  Dynamic LDS above 64 KiB has to be asked for.  The setting belongs to the function on the current device, not to an
+//  object: always the cap's size (`bytes`), so that no object lowers what another one needs.
+inline hipError_t prepare_private(const std::initializer_list<const void *> kernels, const size_t bytes) {
+    for (const void *kernel : kernels) {
+        const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int> (bytes));
+        if (status != hipSuccess) return status;
+    }
+    return hipSuccess;
 }
 
 }  // namespace sums

@@ -33,16 +33,13 @@
 #include "../../include/gf_hip.h"
 #include "plan.hpp"
 
-#include "cell_launch.hpp"
-#include "confinement_host.hpp"
 #include "converge_state.hpp"
-#include "flux_label.hpp"
 #include "hand_over.hpp"
-#include "moments_host.hpp"
-#include "phase_host.hpp"
-#include "ray_batches.hpp"
-#include "source_host.hpp"
-#include "superacc.hpp"
+#include "runtime.hpp"
+
+using namespace gfhip::runtime;
+
+thread_local std::string gfhip::runtime::creation_error;
 
 namespace gfhip {
 void launch_max_reduce(const void *in, const size_t n, const bool f64,
@@ -53,45 +50,8 @@ void launch_max_modulus(const void *in, const size_t n, const bool f64, void *re
 
 namespace {
 
-thread_local std::string creation_error;
-
-//  Owning holders of HIP resources: destruction releases them.
-template<typename H, hipError_t (*release)(H)>
-struct releaser {
-    void operator()(H handle) const { (void)release(handle); }
-};
-template<typename T = void> using device_ptr = std::unique_ptr<T, releaser<void *, hipFree>>;
-template<typename T = void> using host_ptr = std::unique_ptr<T, releaser<void *, hipHostFree>>;       // pinned
-using module_ptr = std::unique_ptr<std::remove_pointer_t<hipModule_t>, releaser<hipModule_t, hipModuleUnload>>;
-using event_ptr = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, releaser<hipEvent_t, hipEventDestroy>>;
-using stream_ptr = std::unique_ptr<std::remove_pointer_t<hipStream_t>, releaser<hipStream_t, hipStreamDestroy>>;
-
-template<typename T>
-hipError_t allocate(device_ptr<T> &p, const size_t bytes) {
-    void *raw = nullptr;
-    const hipError_t status = hipMalloc(&raw, bytes);
-    if (status == hipSuccess) p.reset(static_cast<T *> (raw));
-    return status;
-}
-
-template<typename T>
-hipError_t allocate(host_ptr<T> &p, const size_t bytes) {
-    void *raw = nullptr;
-    const hipError_t status = hipHostMalloc(&raw, bytes, hipHostMallocDefault);
-    if (status == hipSuccess) p.reset(static_cast<T *> (raw));
-    return status;
-}
-
 struct event_pair {
     event_ptr start, stop;
-};
-
-struct buffer {
-    device_ptr<> owned;         // null for a buffer adopted by gfhip_set_buffer, which is never freed here
-    void *pointer = nullptr;
-    size_t count = 0;
-    uint32_t dtype = GFIR_F64;
-    host_ptr<> mirror;          // host copy handed out by gfhip_get_host_buffer, refreshed by gfhip_wait
 };
 
 std::string library_directory() {
@@ -126,45 +86,6 @@ std::string hash_name(const uint64_t hash) {
 }
 
 }  // namespace
-
-//  Members are released last to first: the kernels and buffers, then the owned stream.
-struct gfhip_context {
-    int device = 0;
-    stream_ptr own_stream;                         // set when the context created `stream`
-    hipStream_t stream = nullptr;
-    unsigned int num_cus = 256;
-    device_ptr<unsigned long long> device_scalar;  // 8 words: one per pass of a batch
-    host_ptr<unsigned long long> host_scalar;      // 8 words
-    device_ptr<unsigned int> device_flags;         // bit 0: a lane redid a pass with the compiler's division
-    device_ptr<gfhip::converge_state> device_converge;
-    host_ptr<gfhip::converge_state> host_converge;
-    std::map<uint64_t, buffer> buffers;
-    std::map<uint64_t, device_ptr<>> random_states;    // MT19937 states per random_state node (raw bytes)
-    std::vector<std::unique_ptr<gfhip_kernel>> kernels;
-    std::vector<std::unique_ptr<gfhip_bins>> bins;     // deposition grids (gfhip_bins_create), until gfhip_bins_destroy
-    std::vector<std::unique_ptr<gfhip_flux>> fluxes;   // flux profiles (gfhip_flux_create), until gfhip_flux_destroy
-    std::vector<std::unique_ptr<gfhip_spectrum>> spectra;      // spectra (gfhip_spectrum_create), until gfhip_spectrum_destroy
-    std::vector<std::unique_ptr<gfhip_phase>> phases;          // distributions (gfhip_phase_create), until gfhip_phase_destroy
-    std::vector<std::unique_ptr<gfhip_confine>> confines;      // trackers (gfhip_confine_create), until gfhip_confine_destroy
-    std::vector<std::unique_ptr<gfhip_moments>> moments;       // moment profiles (gfhip_moments_create), until gfhip_moments_destroy
-    std::vector<std::unique_ptr<gfhip_source>> sources;        // particle sources (gfhip_source_create), until gfhip_source_destroy
-    std::string error;
-    gfhip_kernel *running_ahead = nullptr;         // the kernel whose last batch ran passes the caller has not asked for yet
-    gfhip_kernel *max_streak = nullptr;            // the kernel the last entry point was gfhip_run_max of
-    unsigned int timing = 0;                       // 0 = off, N = events around every Nth launch of a kernel
-    event_ptr hand_over_before, hand_over_after;   // order gfhip_hand_over into this context from another stream (made on first use)
-
-    int fail(const std::string &message) {
-        error = message;
-        return 1;
-    }
-    int check(const hipError_t status, const char *what) {
-        if (status != hipSuccess) {
-            return fail(std::string(what) + ": " + hipGetErrorString(status));
-        }
-        return 0;
-    }
-};
 
 //  One compiled kernel of a work item: the item itself, one segment of it (segments.hpp) or its redo launch,
 //  as planned (`plan`: the piece as an item and what its symbols and outputs are; `low`: its text) and as loaded.
@@ -210,114 +131,9 @@ struct gfhip_kernel {
     std::vector<double> samples;                   // durations drained by the last gfhip_kernel_timing
 };
 
-//  A store of exact sums, what a deposition grid and a flux profile both are: per cell the 67 limbs of superacc.hpp,
-//  [cell][limb], and what became of the samples.  The entry points check their own arguments and call these.
-struct exact_cells {
-    gfhip_context *ctx = nullptr;
-    size_t cells = 0;
-    device_ptr<> state;
-    device_ptr<unsigned long long> counters;           // samples, outside, skipped
-    device_ptr<double> rounded;                        // what read() copies out (allocated by the first read)
-    uint64_t pending = 0;                              // deposits since the state was last canonical
-
-    int create(gfhip_context *context, size_t count);  // allocated and zero
-    int normalise();
-    template<typename LAUNCH> int add(size_t count, LAUNCH launch);
-    int counts(uint64_t *samples, uint64_t *outside, uint64_t *skipped);
-    int state_to(int64_t *limbs);
-    int merge(const int64_t *limbs, uint64_t samples, uint64_t outside, uint64_t skipped);
-    int read(double divisor, double *values);
-};
-
-//  A 3-D deposition grid.
-struct gfhip_bins : exact_cells {
-    int n[3] = {0, 0, 0};
-    double scale[3] = {0.0, 0.0, 0.0};                 // n/(last edge - first edge): the kernel's first guess of a cell
-    device_ptr<double> edges;                          // the three axes' edges one after the other
-};
-
-//  What a flux-surface profile and a spectrum share: the map, the psi tables as [table cell][16], the edges the
-//  deposit kernel stages in LDS and the shape of its launches.
-struct flux_cells : exact_cells {
-    gfhip::flux::map map = {};
-    device_ptr<double> packed, edges;
-    bool is_private = false;
-    size_t cap = 0, max_workgroups = 0, lds_bytes = 0;
-    unsigned int block = 0;
-//  Batches of rays (ray_batches.hpp): 0 for a plain object; otherwise the state is [batch][cell][limb], `cells` counts
-//  all of them and `slab` those of one batch, which the launch shape is decided by.
-    size_t batches = 0, slab = 0;
-
-    int create(gfhip_context *context, const gfhip_flux_map *given, size_t count, const std::vector<double> &all_edges,
-               hipError_t (*prepare)(), size_t batch_count = 0);
-    void info_to(struct gfhip_flux_info *info) const;
-    const char *rays_refused(uint64_t first_ray, size_t count) const;
-    const char *particles_refused(uint64_t first_particle, size_t count) const;
-};
-
-//  A flux-surface profile.
-struct gfhip_flux : flux_cells {
-    double scale = 0.0;                                // cells/(last edge - first edge)
-};
-
-//  A spectrum over the flux label and N: cell is*nn + in; the edges of the label, then those of N; fpol as [interval][4].
-struct gfhip_spectrum : flux_cells {
-    gfhip::flux::field field = {};
-    size_t ns = 0, nn = 0;
-    double sscale = 0.0, nscale = 0.0;
-    device_ptr<double> fpol;
-};
-
-//  A distribution of particles over the flux label, the pitch cosine and gamma: cell (is*np + ip)*ng + ig; the three
-//  axes' edges one after the other; fpol as [interval][4].
-struct gfhip_phase : flux_cells {
-    gfhip::flux::field field = {};
-    size_t n[3] = {0, 0, 0};
-    double scale[3] = {0.0, 0.0, 0.0};
-    device_ptr<double> fpol;
-};
-
-//  A first-exit tracker of the particles of one push (confinement.hip): per particle lost_step and the context buffer
-//  `alive_key`; per check its step (here) and the number of particles it found lost (on the device); the footprint of
-//  the losses, cell (ir*nz + iz)*ng + ig, the three axes' edges one after the other.
-struct gfhip_confine : flux_cells {
-    double limit = 0.0;
-    size_t n[3] = {0, 0, 0};
-    double scale[3] = {0.0, 0.0, 0.0};
-    size_t count = 0, capacity = 0;
-    bool is_f32 = false;
-    uint64_t alive_key = 0;
-    device_ptr<uint32_t> lost_step;
-    device_ptr<unsigned long long> newly_lost;         // [capacity]
-    std::vector<uint32_t> steps;                       // the checks made
-    bool exit_ready = false;                           // the exit buffers of `exit_keys` hold NaN for every confined particle
-    uint64_t exit_keys[2] = {0, 0};
-};
-
-//  The moments of particles per flux surface (moment_bins.hip): cell is*4 + k, k = density, current, energy, radiation;
-//  the edges of the label; fpol as [interval][4].
-struct gfhip_moments : flux_cells {
-    gfhip::flux::field field = {};
-    size_t ns = 0;
-    double sscale = 0.0;
-    device_ptr<double> fpol;
-};
-
-//  A particle source (particle_source.hip): the map and the field as a distribution holds them, the profile's edges and
-//  then its probabilities, and the counters placed, unplaced, position_tries, gyro_tries.
-struct gfhip_source {
-    gfhip_context *ctx = nullptr;
-    gfhip::flux::map map = {};
-    gfhip::flux::field field = {};
-    gfhip::draw::parameters par = {};
-    device_ptr<double> packed, fpol, profile;
-    double scale = 0.0;                                // ns/(last edge - first edge)
-    bool is_f32 = false, refill = false;
-    size_t max_workgroups = 0;
-    device_ptr<unsigned long long> counters;
-};
-
-#define GFHIP_TRY(ctx, call, what) do { if ((ctx)->check((call), (what))) return 1; } while (0)
+//  Here, where gfhip_kernel is complete (runtime.hpp).
+gfhip_context::gfhip_context() = default;
+gfhip_context::~gfhip_context() = default;
 
 extern "C" int gfhip_max_concurrency(void) {
     int count = 0;
@@ -698,7 +514,7 @@ static int settle(gfhip_context *ctx);
 //  Entry points that touch the device begin here: the context's device, then the state settled.  gfhip_run_max
 //  settles only when it does not continue a streak (run_max_ahead); gfhip_compile, gfhip_allocate_buffer and
 //  gfhip_kernel_timing look at no state and set the device alone.
-static int enter(gfhip_context *ctx) {
+int gfhip::runtime::enter(gfhip_context *ctx) {
     GFHIP_TRY(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     return settle(ctx);
 }
@@ -721,8 +537,8 @@ extern "C" int gfhip_compile(gfhip_context *ctx) {
     return 0;
 }
 
-static int ensure_buffer(gfhip_context *ctx, const uint64_t key, const size_t count, const uint32_t dtype,
-                         const void *init, size_t init_count = ~static_cast<size_t> (0)) {
+int gfhip::runtime::ensure_buffer(gfhip_context *ctx, const uint64_t key, const size_t count, const uint32_t dtype,
+                                  const void *init, size_t init_count) {
     auto found = ctx->buffers.find(key);
     if (found == ctx->buffers.end()) {
         buffer b;
@@ -1320,7 +1136,7 @@ extern "C" int gfhip_get_flags(gfhip_context *ctx, unsigned int *flags) {
     return 0;
 }
 
-static buffer *find_buffer(gfhip_context *ctx, const uint64_t key) {
+buffer *gfhip::runtime::find_buffer(gfhip_context *ctx, const uint64_t key) {
     auto found = ctx->buffers.find(key);
     if (found == ctx->buffers.end()) {
         ctx->error = "unknown buffer key";
@@ -1580,1715 +1396,5 @@ extern "C" int gfhip_kernel_timing_samples(gfhip_kernel *k, double *ms, size_t c
     const size_t n = k->samples.size() < capacity ? k->samples.size() : capacity;
     if (ms && n) std::memcpy(ms, k->samples.data(), n*sizeof(double));
     if (count) *count = k->samples.size();
-    return 0;
-}
-
-//  Stores of exact sums (cell_launch.hpp, superacc.hpp): what deposition grids and flux profiles share.
-int exact_cells::create(gfhip_context *context, const size_t count) {
-    ctx = context;
-    cells = count;
-    const size_t bytes = cells*gfhip::superacc::limbs*sizeof(int64_t);
-    return ctx->check(allocate(state, bytes), "hipMalloc(cells)") ||
-           ctx->check(hipMemset(state.get(), 0, bytes), "hipMemset(cells)") ||
-           ctx->check(allocate(counters, 3*sizeof(unsigned long long)), "hipMalloc(counters)") ||
-           ctx->check(hipMemset(counters.get(), 0, 3*sizeof(unsigned long long)), "hipMemset(counters)");
-}
-
-//  The state canonical in place: before the deposits since the last time could reach 2^30 (a limb takes 2^31),
-//  before the state is handed out and before it is rounded.  Later deposits add to the canonical digits.
-int exact_cells::normalise() {
-    gfhip::launch_cells_normalise(state.get(), cells, ctx->stream);
-    pending = 0;
-    return ctx->check(hipGetLastError(), "normalise launch");
-}
-
-//  `count` deposits, `launch(first, piece)` enqueueing those of the samples first .. first + piece: at most 2^30
-//  between two normalisations (superacc.hpp); a workgroup-private limb sees fewer than its launch.
-template<typename LAUNCH>
-int exact_cells::add(const size_t count, LAUNCH launch) {
-    if (enter(ctx)) return 1;
-    for (size_t first = 0; first < count;) {
-        const size_t piece = std::min<size_t> (count - first, gfhip::superacc::deposits_per_normalise);
-        if (pending + piece > gfhip::superacc::deposits_per_normalise && normalise()) return 1;
-        launch(first, piece);
-        GFHIP_TRY(ctx, hipGetLastError(), "deposit launch");
-        pending += piece;
-        first += piece;
-    }
-    return 0;
-}
-
-int exact_cells::counts(uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    if (enter(ctx)) return 1;
-    unsigned long long host[3] = {0, 0, 0};
-    GFHIP_TRY(ctx, hipMemcpyAsync(host, counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    if (samples) *samples = host[0];
-    if (outside) *outside = host[1];
-    if (skipped) *skipped = host[2];
-    return 0;
-}
-
-int exact_cells::state_to(int64_t *limbs) {
-    if (enter(ctx) || normalise()) return 1;
-    GFHIP_TRY(ctx, hipMemcpyAsync(limbs, state.get(), cells*gfhip::superacc::limbs*sizeof(int64_t), hipMemcpyDeviceToHost,
-                                  ctx->stream), "hipMemcpyAsync(cells)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return 0;
-}
-
-int exact_cells::merge(const int64_t *limbs, const uint64_t samples, const uint64_t outside, const uint64_t skipped) {
-    if (enter(ctx)) return 1;
-    const size_t words = cells*gfhip::superacc::limbs;
-    const unsigned long long incoming[3] = {samples, outside, skipped};
-    device_ptr<> other;                                // the incoming limbs, then the three counts
-    GFHIP_TRY(ctx, allocate(other, (words + 3)*sizeof(int64_t)), "hipMalloc(merge)");
-    char *counts_at = static_cast<char *> (other.get()) + words*sizeof(int64_t);
-    GFHIP_TRY(ctx, hipMemcpyAsync(other.get(), limbs, words*sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
-    GFHIP_TRY(ctx, hipMemcpyAsync(counts_at, incoming, sizeof(incoming), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(merge)");
-//  Canonical digits (below 2^32) on top of a state that 2^30 deposits may have reached: still inside a limb.
-    gfhip::launch_cells_merge(state.get(), other.get(), words, ctx->stream);
-    gfhip::launch_cells_merge(counters.get(), counts_at, 3, ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "merge launch");
-    if (normalise()) return 1;
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");      // `other` is freed on return
-    return 0;
-}
-
-int exact_cells::read(const double divisor, double *values) {
-    if (enter(ctx)) return 1;
-    if (!rounded) GFHIP_TRY(ctx, allocate(rounded, cells*sizeof(double)), "hipMalloc(rounded cells)");
-    if (normalise()) return 1;
-    gfhip::launch_cells_round(state.get(), cells, divisor, rounded.get(), ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "round launch");
-    GFHIP_TRY(ctx, hipMemcpyAsync(values, rounded.get(), cells*sizeof(double), hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpyAsync(rounded cells)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return 0;
-}
-
-//  Whether the n + 1 edges of an axis are finite and strictly increasing.
-static bool edges_increase(const double *edges, const size_t n) {
-    for (size_t i = 0; i <= n; i++) {
-        if (!std::isfinite(edges[i]) || (i && !(edges[i - 1] < edges[i]))) return false;
-    }
-    return true;
-}
-
-//  N fp64 buffers of at least `count` elements, or the message about `noun`; nothing is enqueued.
-template<size_t N>
-static int fp64_columns(gfhip_context *ctx, const char *noun, const uint64_t (&keys)[N], const size_t count, double **columns) {
-    for (size_t c = 0; c < N; c++) {
-        const buffer *found = find_buffer(ctx, keys[c]);
-        if (!found) return 1;
-        if (found->dtype != GFIR_F64) return ctx->fail(std::string(noun) + " takes fp64 buffers");
-        if (found->count < count) return ctx->fail(std::string(noun) + " buffer is shorter than the sample count");
-        columns[c] = static_cast<double *> (found->pointer);
-    }
-    return 0;
-}
-
-//  gfhip_*_destroy: behind everything the context has queued, out of the context's list.
-template<typename T>
-static void destroy_in(std::vector<std::unique_ptr<T>> gfhip_context::*list, T *object) {
-    if (!object) return;
-    gfhip_context *ctx = object->ctx;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    auto &owned = ctx->*list;
-    for (auto it = owned.begin(); it != owned.end(); ++it) {
-        if (it->get() == object) {
-            owned.erase(it);
-            return;
-        }
-    }
-}
-
-//  Deposition grids (deposition.hip).  The limits of a grid: at most 2047 cells per axis, so that the
-//  three axes' edges (3 x 2048 doubles, 48 KiB) fit the LDS a workgroup gets without asking; at most 2^25 cells
-//  (536 B each: 16.8 GiB of state), so that cell*64 + limb fits the 32-bit key the deposit kernel compares.
-static const size_t bins_axis_limit = 2047, bins_cell_limit = static_cast<size_t> (1) << 25;
-
-extern "C" gfhip_bins *gfhip_bins_create(gfhip_context *ctx, const double *xedges, size_t nx,
-                                         const double *yedges, size_t ny, const double *zedges, size_t nz) {
-    if (!ctx) return nullptr;
-    const double *axes[3] = {xedges, yedges, zedges};
-    const size_t n[3] = {nx, ny, nz};
-    std::vector<double> edges;
-    size_t cells = 1;
-    for (int a = 0; a < 3; a++) {
-        if (!axes[a] || n[a] < 1 || n[a] > bins_axis_limit) {
-            ctx->fail("a deposition grid has 1 to 2047 cells per axis");
-            return nullptr;
-        }
-        if (!edges_increase(axes[a], n[a])) {
-            ctx->fail("the edges of a deposition grid must be finite and strictly increasing");
-            return nullptr;
-        }
-        edges.insert(edges.end(), axes[a], axes[a] + n[a] + 1);
-        cells *= n[a];
-    }
-    if (cells > bins_cell_limit) {
-        ctx->fail("a deposition grid has at most 2^25 cells (536 B each)");
-        return nullptr;
-    }
-    if (ctx->check(hipSetDevice(ctx->device), "hipSetDevice")) return nullptr;
-    std::unique_ptr<gfhip_bins> b(new gfhip_bins);
-    for (int a = 0; a < 3; a++) {
-        b->n[a] = static_cast<int> (n[a]);
-        b->scale[a] = static_cast<double> (n[a])/(axes[a][n[a]] - axes[a][0]);
-    }
-    if (ctx->check(allocate(b->edges, edges.size()*sizeof(double)), "hipMalloc(edges)") ||
-        ctx->check(hipMemcpy(b->edges.get(), edges.data(), edges.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
-        b->create(ctx, cells)) {
-        return nullptr;
-    }
-    ctx->bins.push_back(std::move(b));
-    return ctx->bins.back().get();
-}
-
-extern "C" void gfhip_bins_destroy(gfhip_bins *b) {
-    destroy_in(&gfhip_context::bins, b);
-}
-
-extern "C" int gfhip_bins_add(gfhip_bins *b, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count) {
-    if (!b) return 1;
-    double *columns[4];
-    if (fp64_columns(b->ctx, "a deposition grid", {x_key, y_key, z_key, value_key}, count, columns)) return 1;
-    return b->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_deposit(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
-                              b->edges.get(), b->n[0], b->n[1], b->n[2], b->scale, b->state.get(), b->counters.get(),
-                              b->ctx->num_cus, b->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_bins_counts(gfhip_bins *b, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    return b ? b->counts(samples, outside, skipped) : 1;
-}
-
-extern "C" int gfhip_bins_state(gfhip_bins *b, int64_t *limbs) {
-    if (!b) return 1;
-    if (!limbs) return b->ctx->fail("gfhip_bins_state needs a destination");
-    return b->state_to(limbs);
-}
-
-extern "C" int gfhip_bins_merge(gfhip_bins *b, const int64_t *limbs, uint64_t samples, uint64_t outside, uint64_t skipped) {
-    if (!b) return 1;
-    if (!limbs) return b->ctx->fail("gfhip_bins_merge needs a state");
-    return b->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_bins_read(gfhip_bins *b, double divisor, double *bins) {
-    if (!b) return 1;
-    if (!bins) return b->ctx->fail("gfhip_bins_read needs a destination");
-    return b->read(divisor, bins);
-}
-
-//  Flux profiles (flux_profile.hip, flux_label.hpp).  At most 4096 cells: the edges are staged in LDS on both paths.
-static const size_t flux_cell_limit = 4096;
-
-//  The scalars of a caller's map, or why it is refused.
-static const char *flux_map_of(const gfhip_flux_map *given, gfhip::flux::map &m) {
-    if (!given->coefficients) return "a flux map needs its 16 coefficient tables";
-    if (given->numr == 0 || given->numz == 0) return "a flux map needs numr >= 1 and numz >= 1";
-    const uint64_t table_limit = 1ull << 31;
-    if (given->numr > table_limit || given->numz > table_limit || given->numr*given->numz > table_limit) {
-        return "a flux map's table has at most 2^31 cells";
-    }
-    if (!std::isfinite(given->dr) || given->dr == 0.0 || !std::isfinite(given->dz) || given->dz == 0.0 ||
-        !std::isfinite(given->span) || given->span == 0.0) {
-        return "dr, dz and span of a flux map must be finite and non-zero";
-    }
-    if (!std::isfinite(given->rmin) || !std::isfinite(given->zmin) || !std::isfinite(given->psi0)) {
-        return "rmin, zmin and psi0 of a flux map must be finite";
-    }
-    if (given->flags & ~gfhip::flux::known_flags) return "unknown flag bits in a flux map";
-    if (given->reserved != 0) return "the reserved field of a flux map must be 0";
-    m.rmin = given->rmin;
-    m.dr = given->dr;
-    m.zmin = given->zmin;
-    m.dz = given->dz;
-    m.numr = static_cast<double> (given->numr);
-    m.numz = static_cast<double> (given->numz);
-    m.columns = given->numz;
-    m.psi0 = given->psi0;
-    m.span = given->span;
-    m.flags = given->flags;
-    return nullptr;
-}
-
-//  The 16 psi tables as [table cell][16]: a lane's coefficients are one 128-byte line.  False: no memory.
-static bool psi_lines(const gfhip_flux_map *given, std::vector<double> &lines) {
-    const size_t table = static_cast<size_t> (given->numr*given->numz);
-    try {
-        lines.resize(table*16);
-    } catch (const std::bad_alloc &) {
-        return false;
-    }
-    for (size_t k = 0; k < 16; k++) {
-        const double *from = given->coefficients + k*table;
-        for (size_t at = 0; at < table; at++) lines[at*16 + k] = from[at];
-    }
-    return true;
-}
-
-//  The map checked and copied, its tables repacked to [table cell][16] (a lane's coefficients are one 128-byte line) and
-//  uploaded with the edges, the launch shape decided and the `count` cells allocated.  prepare: the deposit kernels'
-//  request for large dynamic LDS, made when the private path is taken.
-//  batch_count: 0, or the batches of rays a batched object keeps `count` cells each for.
-int flux_cells::create(gfhip_context *context, const gfhip_flux_map *given, const size_t count,
-                       const std::vector<double> &all_edges, hipError_t (*prepare)(), const size_t batch_count) {
-    if (const char *refused = flux_map_of(given, map)) return context->fail(refused);
-    if (context->check(hipSetDevice(context->device), "hipSetDevice")) return 1;
-    batches = batch_count;
-    slab = count;
-    gfhip::flux_launch_shape(count, all_edges.size(), !(given->flags & gfhip::flux::flag_no_private_sums), context->num_cus,
-                             &is_private, &cap, &block, &max_workgroups, &lds_bytes);
-    std::vector<double> lines;
-    if (!psi_lines(given, lines)) return context->fail("a flux map's tables do not fit the host's memory");
-    return context->check(allocate(packed, lines.size()*sizeof(double)), "hipMalloc(flux tables)") ||
-           context->check(hipMemcpy(packed.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
-           context->check(allocate(edges, all_edges.size()*sizeof(double)), "hipMalloc(edges)") ||
-           context->check(hipMemcpy(edges.get(), all_edges.data(), all_edges.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(edges)") ||
-           exact_cells::create(context, batch_count ? batch_count*count : count) ||
-           (is_private && context->check(prepare(), "hipFuncSetAttribute(flux deposit)"));
-}
-
-//  The batches of a batched object, or why they are refused: 1 to 256, and at most 2^20 cells in all.
-static const char *batches_refused(const size_t batch_count, const size_t count) {
-    if (batch_count < 1 || batch_count > gfhip::batches::max_batches) return "a batched object has 1 to 256 batches";
-    if (batch_count*count > (static_cast<size_t> (1) << 20)) return "batches x cells is at most 2^20 (536 B each)";
-    return nullptr;
-}
-
-//  Why an add with a ray index is refused: only a batched object takes one, and first_ray + count fits 64 bits.
-const char *flux_cells::rays_refused(const uint64_t first_ray, const size_t count) const {
-    if (!batches) return "only a batched object (gfhip_flux_create_batched, gfhip_spectrum_create_batched) takes samples with a ray index";
-    if (first_ray + static_cast<uint64_t> (count) < first_ray) return "first_ray + count overflows 64 bits";
-    return nullptr;
-}
-
-//  The same for an add with a particle index (distributions and moment profiles).
-const char *flux_cells::particles_refused(const uint64_t first_particle, const size_t count) const {
-    if (!batches) return "only a batched object (gfhip_phase_create_batched, gfhip_moments_create_batched) takes particles with their index";
-    if (first_particle + static_cast<uint64_t> (count) < first_particle) return "first_particle + count overflows 64 bits";
-    return nullptr;
-}
-
-void flux_cells::info_to(struct gfhip_flux_info *info) const {
-    info->private_sums = is_private ? 1u : 0u;
-    info->workgroup_size = block;
-    info->cap_cells = cap;
-    info->max_workgroups = max_workgroups;
-    info->lds_bytes = lds_bytes;
-}
-
-//  batch_count: 0 for gfhip_flux_create.
-static gfhip_flux *flux_create(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, const size_t cells,
-                               const size_t batch_count) {
-    if (!map || !edges) {
-        ctx->fail("a flux profile needs a map and edges");
-        return nullptr;
-    }
-    if (cells < 1 || cells > flux_cell_limit) {
-        ctx->fail("a flux profile has 1 to 4096 cells");
-        return nullptr;
-    }
-    if (!edges_increase(edges, cells)) {
-        ctx->fail("the edges of a flux profile must be finite and strictly increasing");
-        return nullptr;
-    }
-    std::unique_ptr<gfhip_flux> f(new gfhip_flux);
-    f->scale = static_cast<double> (cells)/(edges[cells] - edges[0]);
-    if (f->create(ctx, map, cells, std::vector<double> (edges, edges + cells + 1), gfhip::flux_prepare, batch_count)) return nullptr;
-    ctx->fluxes.push_back(std::move(f));
-    return ctx->fluxes.back().get();
-}
-
-extern "C" gfhip_flux *gfhip_flux_create(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, size_t cells) {
-    return ctx ? flux_create(ctx, map, edges, cells, 0) : nullptr;
-}
-
-extern "C" gfhip_flux *gfhip_flux_create_batched(gfhip_context *ctx, const gfhip_flux_map *map, const double *edges, size_t cells,
-                                                 size_t batches) {
-    if (!ctx) return nullptr;
-    if (const char *refused = batches_refused(batches, cells)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    return flux_create(ctx, map, edges, cells, batches);
-}
-
-extern "C" void gfhip_flux_destroy(gfhip_flux *f) {
-    destroy_in(&gfhip_context::fluxes, f);
-}
-
-extern "C" int gfhip_flux_add(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count) {
-    if (!f) return 1;
-    if (f->batches) return f->ctx->fail("a batched flux profile takes its samples with their ray index: gfhip_flux_add_rays");
-    double *columns[4];
-    if (fp64_columns(f->ctx, "a flux profile", {x_key, y_key, z_key, value_key}, count, columns)) return 1;
-    return f->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_flux_deposit(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
-                                   f->map, f->packed.get(), f->edges.get(), f->cells, f->scale, f->is_private, f->block,
-                                   f->max_workgroups, f->lds_bytes, f->state.get(), f->counters.get(), f->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_flux_add_rays(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t value_key, size_t count,
-                                   uint64_t first_ray) {
-    if (!f) return 1;
-    if (const char *refused = f->rays_refused(first_ray, count)) return f->ctx->fail(refused);
-    double *columns[4];
-    if (fp64_columns(f->ctx, "a flux profile", {x_key, y_key, z_key, value_key}, count, columns)) return 1;
-    return f->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_flux_deposit_rays(columns[0] + first, columns[1] + first, columns[2] + first, columns[3] + first, piece,
-                                        first_ray + first, f->batches, f->map, f->packed.get(), f->edges.get(), f->slab,
-                                        f->scale, f->is_private, f->block, f->max_workgroups, f->lds_bytes, f->state.get(),
-                                        f->counters.get(), f->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_flux_label(gfhip_flux *f, uint64_t x_key, uint64_t y_key, uint64_t z_key, uint64_t label_key, size_t count) {
-    if (!f) return 1;
-    gfhip_context *ctx = f->ctx;
-    double *columns[4];
-    if (fp64_columns(ctx, "a flux profile", {x_key, y_key, z_key, label_key}, count, columns)) return 1;
-    if (enter(ctx)) return 1;
-    gfhip::launch_flux_label(columns[0], columns[1], columns[2], count, f->map, f->packed.get(), columns[3], ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "flux label launch");
-    return 0;
-}
-
-extern "C" int gfhip_flux_counts(gfhip_flux *f, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    return f ? f->counts(samples, outside, skipped) : 1;
-}
-
-extern "C" int gfhip_flux_state(gfhip_flux *f, int64_t *limbs) {
-    if (!f) return 1;
-    if (!limbs) return f->ctx->fail("gfhip_flux_state needs a destination");
-    return f->state_to(limbs);
-}
-
-extern "C" int gfhip_flux_merge(gfhip_flux *f, const int64_t *limbs, size_t cells, uint64_t samples, uint64_t outside, uint64_t skipped) {
-    if (!f) return 1;
-    if (!limbs) return f->ctx->fail("gfhip_flux_merge needs a state");
-    if (f->batches || cells != f->cells) return f->ctx->fail("merge: a flux profile of another shape");
-    return f->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_flux_merge_batches(gfhip_flux *f, const int64_t *limbs, size_t batches, size_t cells, uint64_t samples,
-                                        uint64_t outside, uint64_t skipped) {
-    if (!f) return 1;
-    if (!limbs) return f->ctx->fail("gfhip_flux_merge_batches needs a state");
-    if (!f->batches || batches != f->batches || cells != f->slab) return f->ctx->fail("merge: a flux profile of another shape");
-    return f->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_flux_read(gfhip_flux *f, double divisor, double *values) {
-    if (!f) return 1;
-    if (!values) return f->ctx->fail("gfhip_flux_read needs a destination");
-    return f->read(divisor, values);
-}
-
-//  Not through enter(): it reads what gfhip_flux_create decided on the host and touches neither the device nor the stream.
-extern "C" int gfhip_flux_info(gfhip_flux *f, struct gfhip_flux_info *info) {
-    if (!f) return 1;
-    if (!info) return f->ctx->fail("gfhip_flux_info needs a destination");
-    f->info_to(info);
-    return 0;
-}
-
-//  Host side, no device: flux_label.hpp on the caller's 16 tables.
-extern "C" int gfhip_flux_label_host(const gfhip_flux_map *map, const double *x, const double *y, const double *z,
-                                     size_t count, double *label) {
-    if (!map || ((!x || !y || !z || !label) && count)) {
-        creation_error = "gfhip_flux_label_host needs a map, three coordinate arrays and a destination";
-        return 1;
-    }
-    gfhip::flux::map m;
-    if (const char *refused = flux_map_of(map, m)) {
-        creation_error = refused;
-        return 1;
-    }
-    const size_t table = static_cast<size_t> (map->numr*map->numz);
-    for (size_t s = 0; s < count; s++) {
-        double tr, tz, c[16];
-        const long long at = gfhip::flux::locate(m, x[s], y[s], z[s], tr, tz);
-        if (at < 0) {
-            label[s] = std::numeric_limits<double>::quiet_NaN();
-            continue;
-        }
-        for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
-        label[s] = gfhip::flux::label_of(m, gfhip::flux::psi_of(c, tr, tz));
-    }
-    return 0;
-}
-
-//  Spectra over the flux label and N (flux_spectrum.hip, flux_label.hpp).  At most 4096 cells per axis and 2^16 in all
-//  (536 B each: 35 MB of state); the two axes' edges are staged in LDS on both paths.
-static const size_t spectrum_cell_limit = static_cast<size_t> (1) << 16;
-
-//  The scalars of a caller's field, or why it is refused.
-static const char *spectrum_field_of(const gfhip_spectrum_field *given, gfhip::flux::field &f) {
-    for (const double *table : given->fpol) {
-        if (!table) return "a spectrum's field needs its four fpol tables";
-    }
-    if (given->numpsi == 0 || given->numpsi > 0x7fffffffull) return "a spectrum's field needs 1 <= numpsi <= 2^31 - 1";
-    if (!std::isfinite(given->dpsi) || given->dpsi == 0.0 || !std::isfinite(given->c) || given->c == 0.0) {
-        return "dpsi and c of a spectrum's field must be finite and non-zero";
-    }
-    if (!std::isfinite(given->psimin)) return "psimin of a spectrum's field must be finite";
-    if (given->reserved != 0) return "the reserved field of a spectrum's field must be 0";
-    f.psimin = given->psimin;
-    f.dpsi = given->dpsi;
-    f.numpsi = static_cast<double> (given->numpsi);
-    f.last = static_cast<int> (given->numpsi - 1);
-    f.c = given->c;
-    return nullptr;
-}
-
-//  The four fpol tables as [interval][4]: a lane's coefficients are one 32-byte line.  False: no memory.
-static bool fpol_lines(const gfhip_spectrum_field *field, std::vector<double> &lines) {
-    try {
-        lines.resize(static_cast<size_t> (field->numpsi)*4);
-    } catch (const std::bad_alloc &) {
-        return false;
-    }
-    for (size_t k = 0; k < 4; k++) {
-        for (size_t q = 0; q < field->numpsi; q++) lines[q*4 + k] = field->fpol[k][q];
-    }
-    return true;
-}
-
-//  batch_count: 0 for gfhip_spectrum_create.
-static gfhip_spectrum *spectrum_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                       const double *sedges, const size_t ns, const double *nedges, const size_t nn,
-                                       const size_t batch_count) {
-    if (!map || !field || !sedges || !nedges) {
-        ctx->fail("a spectrum needs a map, a field and two edge arrays");
-        return nullptr;
-    }
-    if (ns < 1 || ns > flux_cell_limit || nn < 1 || nn > flux_cell_limit) {
-        ctx->fail("a spectrum has 1 to 4096 cells per axis");
-        return nullptr;
-    }
-    if (ns*nn > spectrum_cell_limit) {
-        ctx->fail("a spectrum has at most 65536 cells (536 B each)");
-        return nullptr;
-    }
-    if (!edges_increase(sedges, ns) || !edges_increase(nedges, nn)) {
-        ctx->fail("the edges of a spectrum must be finite and strictly increasing");
-        return nullptr;
-    }
-    std::unique_ptr<gfhip_spectrum> s(new gfhip_spectrum);
-    if (const char *refused = spectrum_field_of(field, s->field)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    s->ns = ns;
-    s->nn = nn;
-    s->sscale = static_cast<double> (ns)/(sedges[ns] - sedges[0]);
-    s->nscale = static_cast<double> (nn)/(nedges[nn] - nedges[0]);
-    std::vector<double> edges(sedges, sedges + ns + 1);
-    edges.insert(edges.end(), nedges, nedges + nn + 1);
-    std::vector<double> lines;
-    if (!fpol_lines(field, lines)) {
-        ctx->fail("a spectrum's fpol tables do not fit the host's memory");
-        return nullptr;
-    }
-    if (s->create(ctx, map, ns*nn, edges, gfhip::spectrum_prepare, batch_count) ||
-        ctx->check(allocate(s->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
-        ctx->check(hipMemcpy(s->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
-        return nullptr;
-    }
-    ctx->spectra.push_back(std::move(s));
-    return ctx->spectra.back().get();
-}
-
-extern "C" gfhip_spectrum *gfhip_spectrum_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                                 const double *sedges, size_t ns, const double *nedges, size_t nn) {
-    return ctx ? spectrum_create(ctx, map, field, sedges, ns, nedges, nn, 0) : nullptr;
-}
-
-extern "C" gfhip_spectrum *gfhip_spectrum_create_batched(gfhip_context *ctx, const gfhip_flux_map *map,
-                                                         const gfhip_spectrum_field *field, const double *sedges, size_t ns,
-                                                         const double *nedges, size_t nn, size_t batches) {
-    if (!ctx) return nullptr;
-//  Either axis has at most 4096 cells (checked below): the product cannot wrap here.
-    if (const char *refused = batches_refused(batches, ns <= flux_cell_limit && nn <= flux_cell_limit ? ns*nn : 0)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    return spectrum_create(ctx, map, field, sedges, ns, nedges, nn, batches);
-}
-
-extern "C" void gfhip_spectrum_destroy(gfhip_spectrum *s) {
-    destroy_in(&gfhip_context::spectra, s);
-}
-
-extern "C" int gfhip_spectrum_add(gfhip_spectrum *s, const uint64_t keys[8], size_t count) {
-    if (!s) return 1;
-    if (!keys) return s->ctx->fail("gfhip_spectrum_add needs its 8 keys");
-    if (s->batches) return s->ctx->fail("a batched spectrum takes its samples with their ray index: gfhip_spectrum_add_rays");
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], keys[7]};
-    double *columns[8];
-    if (fp64_columns(s->ctx, "a spectrum", all, count, columns)) return 1;
-    return s->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_spectrum_deposit(columns, first, piece, s->map, s->field, s->packed.get(), s->fpol.get(), s->edges.get(),
-                                       s->ns, s->nn, s->sscale, s->nscale, s->is_private, s->block, s->max_workgroups,
-                                       s->lds_bytes, s->state.get(), s->counters.get(), s->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_spectrum_add_rays(gfhip_spectrum *s, const uint64_t keys[8], size_t count, uint64_t first_ray) {
-    if (!s) return 1;
-    if (!keys) return s->ctx->fail("gfhip_spectrum_add_rays needs its 8 keys");
-    if (const char *refused = s->rays_refused(first_ray, count)) return s->ctx->fail(refused);
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], keys[7]};
-    double *columns[8];
-    if (fp64_columns(s->ctx, "a spectrum", all, count, columns)) return 1;
-    return s->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_spectrum_deposit_rays(columns, first, piece, first_ray + first, s->batches, s->map, s->field,
-                                            s->packed.get(), s->fpol.get(), s->edges.get(), s->ns, s->nn, s->sscale, s->nscale,
-                                            s->is_private, s->block, s->max_workgroups, s->lds_bytes, s->state.get(),
-                                            s->counters.get(), s->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_spectrum_npar(gfhip_spectrum *s, const uint64_t keys[7], uint64_t label_key, uint64_t npar_key, size_t count) {
-    if (!s) return 1;
-    gfhip_context *ctx = s->ctx;
-    if (!keys) return ctx->fail("gfhip_spectrum_npar needs its 7 keys");
-    const uint64_t all[9] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], label_key, npar_key};
-    double *columns[9];
-    if (fp64_columns(ctx, "a spectrum", all, count, columns)) return 1;
-    if (enter(ctx)) return 1;
-    gfhip::launch_spectrum_npar(columns, count, s->map, s->field, s->packed.get(), s->fpol.get(), columns[7], columns[8], ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "spectrum npar launch");
-    return 0;
-}
-
-extern "C" int gfhip_spectrum_counts(gfhip_spectrum *s, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    return s ? s->counts(samples, outside, skipped) : 1;
-}
-
-extern "C" int gfhip_spectrum_state(gfhip_spectrum *s, int64_t *limbs) {
-    if (!s) return 1;
-    if (!limbs) return s->ctx->fail("gfhip_spectrum_state needs a destination");
-    return s->state_to(limbs);
-}
-
-extern "C" int gfhip_spectrum_merge(gfhip_spectrum *s, const int64_t *limbs, size_t ns, size_t nn, uint64_t samples, uint64_t outside,
-                                    uint64_t skipped) {
-    if (!s) return 1;
-    if (!limbs) return s->ctx->fail("gfhip_spectrum_merge needs a state");
-    if (s->batches || ns != s->ns || nn != s->nn) return s->ctx->fail("merge: a spectrum of another shape");
-    return s->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_spectrum_merge_batches(gfhip_spectrum *s, const int64_t *limbs, size_t batches, size_t ns, size_t nn,
-                                            uint64_t samples, uint64_t outside, uint64_t skipped) {
-    if (!s) return 1;
-    if (!limbs) return s->ctx->fail("gfhip_spectrum_merge_batches needs a state");
-    if (!s->batches || batches != s->batches || ns != s->ns || nn != s->nn) return s->ctx->fail("merge: a spectrum of another shape");
-    return s->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_spectrum_read(gfhip_spectrum *s, double divisor, double *values) {
-    if (!s) return 1;
-    if (!values) return s->ctx->fail("gfhip_spectrum_read needs a destination");
-    return s->read(divisor, values);
-}
-
-//  Not through enter(): as gfhip_flux_info.
-extern "C" int gfhip_spectrum_info(gfhip_spectrum *s, struct gfhip_flux_info *info) {
-    if (!s) return 1;
-    if (!info) return s->ctx->fail("gfhip_spectrum_info needs a destination");
-    s->info_to(info);
-    return 0;
-}
-
-//  Host side, no device: flux_label.hpp on the caller's 16 + 4 tables.
-extern "C" int gfhip_spectrum_npar_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *const columns[7],
-                                        size_t count, double *label, double *npar) {
-    if (!map || !field || !columns || ((!label || !npar) && count)) {
-        creation_error = "gfhip_spectrum_npar_host needs a map, a field, seven columns and two destinations";
-        return 1;
-    }
-    for (int k = 0; k < 7; k++) {
-        if (!columns[k] && count) {
-            creation_error = "gfhip_spectrum_npar_host needs a map, a field, seven columns and two destinations";
-            return 1;
-        }
-    }
-    gfhip::flux::map m;
-    gfhip::flux::field f;
-    const char *refused = flux_map_of(map, m);
-    if (!refused) refused = spectrum_field_of(field, f);
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    const size_t table = static_cast<size_t> (map->numr*map->numz);
-    for (size_t s = 0; s < count; s++) {
-        const double x = columns[0][s], y = columns[1][s];
-        double tr, tz, tp, gr, gz, c[16], cubic[4];
-        const long long at = gfhip::flux::locate(m, x, y, columns[2][s], tr, tz);
-        if (at < 0) {
-            label[s] = npar[s] = std::numeric_limits<double>::quiet_NaN();
-            continue;
-        }
-        for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
-        const double psi = gfhip::flux::psi_gradient(m, c, tr, tz, gr, gz);
-        label[s] = gfhip::flux::canonical(gfhip::flux::label_of(m, psi));
-        const int q = gfhip::flux::fpol_interval(f, psi, tp);
-        for (size_t k = 0; k < 4; k++) cubic[k] = field->fpol[k][q];
-        npar[s] = gfhip::flux::npar_of(f, x, y, gfhip::flux::radius_of(x, y), columns[3][s], columns[4][s], columns[5][s],
-                                       columns[6][s], gr, gz, gfhip::flux::fpol_of(cubic, tp));
-    }
-    return 0;
-}
-
-//  Distributions of particles over the flux label, the pitch cosine and gamma (phase_bins.hip, flux_label.hpp).  At most
-//  4096 cells per axis and 2^20 in all (536 B each: 563 MB of state); the three axes' edges are staged in LDS on both
-//  paths.
-static const size_t phase_cell_limit = static_cast<size_t> (1) << 20;
-
-//  The scalars of a distribution's field: a spectrum's, whose c takes no part here.
-static const char *phase_field_of(const gfhip_spectrum_field *given, gfhip::flux::field &f) {
-    gfhip_spectrum_field without_c = *given;
-    without_c.c = 1.0;
-    return spectrum_field_of(&without_c, f);
-}
-
-//  The label and the pitch cosine of one particle from the caller's 16 + 4 tables, both NaN outside the map.
-static void phase_point(const gfhip::flux::map &m, const gfhip::flux::field &f, const gfhip_flux_map *map,
-                        const gfhip_spectrum_field *field, const double x, const double y, const double z, const double ux,
-                        const double uy, const double uz, double &label, double &pitch) {
-    const size_t table = static_cast<size_t> (map->numr*map->numz);
-    double tr, tz, tp, gr, gz, c[16], cubic[4];
-    const long long at = gfhip::flux::locate(m, x, y, z, tr, tz);
-    if (at < 0) {
-        label = pitch = std::numeric_limits<double>::quiet_NaN();
-        return;
-    }
-    for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
-    const double psi = gfhip::flux::psi_gradient(m, c, tr, tz, gr, gz);
-    label = gfhip::flux::canonical(gfhip::flux::label_of(m, psi));
-    const int q = gfhip::flux::fpol_interval(f, psi, tp);
-    for (size_t k = 0; k < 4; k++) cubic[k] = field->fpol[k][q];
-    pitch = gfhip::flux::pitch_of(x, y, gfhip::flux::radius_of(x, y), ux, uy, uz, gr, gz, gfhip::flux::fpol_of(cubic, tp));
-}
-
-//  batch_count: 0 for gfhip_phase_create.
-static gfhip_phase *phase_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                 const double *sedges, size_t ns, const double *pedges, size_t np,
-                                 const double *gedges, size_t ng, const size_t batch_count, const bool batched) {
-    if (!map || !field || !sedges || !pedges || !gedges) {
-        ctx->fail("a distribution needs a map, a field and three edge arrays");
-        return nullptr;
-    }
-    const double *axes[3] = {sedges, pedges, gedges};
-    const size_t n[3] = {ns, np, ng};
-    std::vector<double> edges;
-    size_t cells = 1;
-    for (int a = 0; a < 3; a++) {
-        if (n[a] < 1 || n[a] > flux_cell_limit) {
-            ctx->fail("a distribution has 1 to 4096 cells per axis (at least two edges)");
-            return nullptr;
-        }
-        if (!edges_increase(axes[a], n[a])) {
-            ctx->fail("the edges of a distribution must be finite and strictly increasing");
-            return nullptr;
-        }
-        edges.insert(edges.end(), axes[a], axes[a] + n[a] + 1);
-        cells *= n[a];                                 // at most 2^36
-    }
-    if (cells > phase_cell_limit) {
-        ctx->fail("a distribution has at most 2^20 cells (536 B each)");
-        return nullptr;
-    }
-    if (const char *refused = batched ? batches_refused(batch_count, cells) : nullptr) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    std::unique_ptr<gfhip_phase> p(new gfhip_phase);
-    if (const char *refused = phase_field_of(field, p->field)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    for (int a = 0; a < 3; a++) {
-        p->n[a] = n[a];
-        p->scale[a] = static_cast<double> (n[a])/(axes[a][n[a]] - axes[a][0]);
-    }
-    std::vector<double> lines;
-    if (!fpol_lines(field, lines)) {
-        ctx->fail("a distribution's fpol tables do not fit the host's memory");
-        return nullptr;
-    }
-    if (p->create(ctx, map, cells, edges, gfhip::phase_prepare, batch_count) ||
-        ctx->check(allocate(p->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
-        ctx->check(hipMemcpy(p->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
-        return nullptr;
-    }
-    ctx->phases.push_back(std::move(p));
-    return ctx->phases.back().get();
-}
-
-extern "C" gfhip_phase *gfhip_phase_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                           const double *sedges, size_t ns, const double *pedges, size_t np,
-                                           const double *gedges, size_t ng) {
-    return ctx ? phase_create(ctx, map, field, sedges, ns, pedges, np, gedges, ng, 0, false) : nullptr;
-}
-
-extern "C" gfhip_phase *gfhip_phase_create_batched(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                                   const double *sedges, size_t ns, const double *pedges, size_t np,
-                                                   const double *gedges, size_t ng, size_t batches) {
-    return ctx ? phase_create(ctx, map, field, sedges, ns, pedges, np, gedges, ng, batches, true) : nullptr;
-}
-
-extern "C" void gfhip_phase_destroy(gfhip_phase *p) {
-    destroy_in(&gfhip_context::phases, p);
-}
-
-//  `used` real buffers of ONE type, fp32 or fp64, of at least `count` elements, or the message; nothing is enqueued.
-static int particle_columns(gfhip_context *ctx, const uint64_t *keys, const size_t used, const size_t count,
-                            const void **columns, bool &is_f32, const char *noun = "a distribution") {
-    uint32_t dtype = 0;
-    for (size_t c = 0; c < used; c++) {
-        const buffer *found = find_buffer(ctx, keys[c]);
-        if (!found) return 1;
-        if (found->dtype != GFIR_F64 && found->dtype != GFIR_F32) return ctx->fail(std::string(noun) + " takes fp32 or fp64 buffers");
-        if (c && found->dtype != dtype) return ctx->fail(std::string(noun) + " takes buffers of one type, all fp32 or all fp64");
-        if (found->count < count) return ctx->fail(std::string(noun) + " buffer is shorter than the particle count");
-        dtype = found->dtype;
-        columns[c] = found->pointer;
-    }
-    is_f32 = dtype == GFIR_F32;
-    return 0;
-}
-
-extern "C" int gfhip_phase_add(gfhip_phase *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count) {
-    if (!p) return 1;
-    if (!keys) return p->ctx->fail("gfhip_phase_add needs its 7 keys");
-    if (p->batches) return p->ctx->fail("a batched distribution takes its particles with their index: gfhip_phase_add_particles");
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
-    const void *columns[8] = {};
-    bool is_f32 = false;
-    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32)) return 1;
-    return p->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_phase_deposit(columns, is_f32, first, piece, p->map, p->field, p->packed.get(), p->fpol.get(),
-                                    p->edges.get(), p->n, p->scale, p->is_private, p->block, p->max_workgroups, p->lds_bytes,
-                                    p->state.get(), p->counters.get(), p->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_phase_add_particles(gfhip_phase *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count,
-                                         uint64_t first_particle) {
-    if (!p) return 1;
-    if (!keys) return p->ctx->fail("gfhip_phase_add_particles needs its 7 keys");
-    if (const char *refused = p->particles_refused(first_particle, count)) return p->ctx->fail(refused);
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
-    const void *columns[8] = {};
-    bool is_f32 = false;
-    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32)) return 1;
-    return p->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_phase_deposit_particles(columns, is_f32, first, piece, first_particle + first, p->batches, p->map, p->field,
-                                              p->packed.get(), p->fpol.get(), p->edges.get(), p->n, p->scale, p->is_private,
-                                              p->block, p->max_workgroups, p->lds_bytes, p->state.get(), p->counters.get(),
-                                              p->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_phase_coordinates(gfhip_phase *p, const uint64_t keys[7], uint64_t label_key, uint64_t pitch_key, size_t count) {
-    if (!p) return 1;
-    gfhip_context *ctx = p->ctx;
-    if (!keys) return ctx->fail("gfhip_phase_coordinates needs its 7 keys");
-    const void *columns[8] = {};
-    bool is_f32 = false;
-    if (particle_columns(ctx, keys, 7, count, columns, is_f32)) return 1;
-    double *out[2];
-    if (fp64_columns(ctx, "a distribution's label and pitch", {label_key, pitch_key}, count, out)) return 1;
-    if (enter(ctx)) return 1;
-    gfhip::launch_phase_coordinates(columns, is_f32, count, p->map, p->field, p->packed.get(), p->fpol.get(), out[0], out[1],
-                                    ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "phase coordinates launch");
-    return 0;
-}
-
-extern "C" int gfhip_phase_counts(gfhip_phase *p, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    return p ? p->counts(samples, outside, skipped) : 1;
-}
-
-extern "C" int gfhip_phase_state(gfhip_phase *p, int64_t *limbs) {
-    if (!p) return 1;
-    if (!limbs) return p->ctx->fail("gfhip_phase_state needs a destination");
-    return p->state_to(limbs);
-}
-
-extern "C" int gfhip_phase_merge(gfhip_phase *p, const int64_t *limbs, size_t ns, size_t np, size_t ng, uint64_t samples,
-                                 uint64_t outside, uint64_t skipped) {
-    if (!p) return 1;
-    if (!limbs) return p->ctx->fail("gfhip_phase_merge needs a state");
-    if (p->batches || ns != p->n[0] || np != p->n[1] || ng != p->n[2]) return p->ctx->fail("merge: a distribution of another shape");
-    return p->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_phase_merge_batches(gfhip_phase *p, const int64_t *limbs, size_t batches, size_t ns, size_t np, size_t ng,
-                                         uint64_t samples, uint64_t outside, uint64_t skipped) {
-    if (!p) return 1;
-    if (!limbs) return p->ctx->fail("gfhip_phase_merge_batches needs a state");
-    if (!p->batches || batches != p->batches || ns != p->n[0] || np != p->n[1] || ng != p->n[2]) {
-        return p->ctx->fail("merge: a distribution of another shape");
-    }
-    return p->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_phase_read(gfhip_phase *p, double divisor, double *values) {
-    if (!p) return 1;
-    if (!values) return p->ctx->fail("gfhip_phase_read needs a destination");
-    return p->read(divisor, values);
-}
-
-//  Not through enter(): as gfhip_flux_info.
-extern "C" int gfhip_phase_info(gfhip_phase *p, struct gfhip_flux_info *info) {
-    if (!p) return 1;
-    if (!info) return p->ctx->fail("gfhip_phase_info needs a destination");
-    p->info_to(info);
-    return 0;
-}
-
-//  Host side, no device: flux_label.hpp on the caller's 16 + 4 tables.
-extern "C" int gfhip_phase_coordinates_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                            const void *const columns[7], int is_f32, size_t count, double *label, double *pitch) {
-    bool complete = map && field && columns && ((label && pitch) || !count);
-    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
-    if (!complete) {
-        creation_error = "gfhip_phase_coordinates_host needs a map, a field, seven columns and two destinations";
-        return 1;
-    }
-    gfhip::flux::map m;
-    gfhip::flux::field f;
-    const char *refused = flux_map_of(map, m);
-    if (!refused) refused = phase_field_of(field, f);
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    for (size_t s = 0; s < count; s++) {
-        double v[6];
-        for (int k = 0; k < 6; k++) {
-            v[k] = is_f32 ? static_cast<double> (static_cast<const float *> (columns[k])[s]) : static_cast<const double *> (columns[k])[s];
-        }
-        phase_point(m, f, map, field, v[0], v[1], v[2], v[3], v[4], v[5], label[s], pitch[s]);
-    }
-    return 0;
-}
-
-//  Moment profiles (moment_bins.hip, flux_label.hpp): four cells per flux surface.  The surfaces are an axis of a
-//  distribution, 1 to 4096 (their edges are staged in LDS on both paths), so the 2^20 cells are never reached by an
-//  accepted axis; the check stands first for callers that ask for more.
-static const size_t moment_count = gfhip::moments::count;
-
-//  The label axis checked, or why it is refused.
-static const char *moments_axis_of(const double *sedges, const size_t ns) {
-    if (ns > phase_cell_limit/moment_count) return "a moment profile has at most 2^20 cells (four per surface, 536 B each)";
-    if (ns < 1 || ns > flux_cell_limit) return "a moment profile has 1 to 4096 surfaces (at least two edges)";
-    if (!edges_increase(sedges, ns)) return "the edges of a moment profile must be finite and strictly increasing";
-    return nullptr;
-}
-
-//  batch_count: 0 for gfhip_moments_create.
-static gfhip_moments *moments_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                     const double *sedges, size_t ns, const size_t batch_count, const bool batched) {
-    if (!map || !field || !sedges) {
-        ctx->fail("a moment profile needs a map, a field and the label edges");
-        return nullptr;
-    }
-    if (const char *refused = moments_axis_of(sedges, ns)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    if (const char *refused = batched ? batches_refused(batch_count, ns*moment_count) : nullptr) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    std::unique_ptr<gfhip_moments> p(new gfhip_moments);
-    if (const char *refused = phase_field_of(field, p->field)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    p->ns = ns;
-    p->sscale = static_cast<double> (ns)/(sedges[ns] - sedges[0]);
-    std::vector<double> lines;
-    if (!fpol_lines(field, lines)) {
-        ctx->fail("a moment profile's fpol tables do not fit the host's memory");
-        return nullptr;
-    }
-    if (p->create(ctx, map, ns*moment_count, std::vector<double> (sedges, sedges + ns + 1), gfhip::moments_prepare, batch_count) ||
-        ctx->check(allocate(p->fpol, lines.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
-        ctx->check(hipMemcpy(p->fpol.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)")) {
-        return nullptr;
-    }
-    ctx->moments.push_back(std::move(p));
-    return ctx->moments.back().get();
-}
-
-extern "C" gfhip_moments *gfhip_moments_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                               const double *sedges, size_t ns) {
-    return ctx ? moments_create(ctx, map, field, sedges, ns, 0, false) : nullptr;
-}
-
-extern "C" gfhip_moments *gfhip_moments_create_batched(gfhip_context *ctx, const gfhip_flux_map *map,
-                                                       const gfhip_spectrum_field *field, const double *sedges, size_t ns,
-                                                       size_t batches) {
-    return ctx ? moments_create(ctx, map, field, sedges, ns, batches, true) : nullptr;
-}
-
-extern "C" void gfhip_moments_destroy(gfhip_moments *p) {
-    destroy_in(&gfhip_context::moments, p);
-}
-
-extern "C" int gfhip_moments_add(gfhip_moments *p, const uint64_t keys[7], uint64_t weight_key, int has_weight, size_t count) {
-    if (!p) return 1;
-    if (!keys) return p->ctx->fail("gfhip_moments_add needs its 7 keys");
-    if (p->batches) return p->ctx->fail("a batched moment profile takes its particles with their index: gfhip_moments_add_particles");
-    if (count == 0) return p->ctx->fail("a moment profile takes at least one particle");
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
-    const void *columns[8] = {};
-    bool is_f32 = false;
-    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32, "a moment profile")) return 1;
-    return p->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_moment_deposit(columns, is_f32, first, piece, p->map, p->field, p->packed.get(), p->fpol.get(),
-                                     p->edges.get(), p->ns, p->sscale, p->is_private, p->block, p->max_workgroups, p->lds_bytes,
-                                     p->state.get(), p->counters.get(), p->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_moments_add_particles(gfhip_moments *p, const uint64_t keys[7], uint64_t weight_key, int has_weight,
-                                           size_t count, uint64_t first_particle) {
-    if (!p) return 1;
-    if (!keys) return p->ctx->fail("gfhip_moments_add_particles needs its 7 keys");
-    if (const char *refused = p->particles_refused(first_particle, count)) return p->ctx->fail(refused);
-    if (count == 0) return p->ctx->fail("a moment profile takes at least one particle");
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
-    const void *columns[8] = {};
-    bool is_f32 = false;
-    if (particle_columns(p->ctx, all, has_weight ? 8 : 7, count, columns, is_f32, "a moment profile")) return 1;
-    return p->add(count, [&](const size_t first, const size_t piece) {
-        gfhip::launch_moment_deposit_particles(columns, is_f32, first, piece, first_particle + first, p->batches, p->map, p->field,
-                                               p->packed.get(), p->fpol.get(), p->edges.get(), p->ns, p->sscale, p->is_private,
-                                               p->block, p->max_workgroups, p->lds_bytes, p->state.get(), p->counters.get(),
-                                               p->ctx->stream);
-    });
-}
-
-extern "C" int gfhip_moments_values(gfhip_moments *p, const uint64_t keys[7], uint64_t label_key, uint64_t values_key, size_t count) {
-    if (!p) return 1;
-    gfhip_context *ctx = p->ctx;
-    if (!keys) return ctx->fail("gfhip_moments_values needs its 7 keys");
-    if (count == 0) return ctx->fail("a moment profile takes at least one particle");
-    if (count > std::numeric_limits<size_t>::max()/moment_count) return ctx->fail("a moment profile's values buffer is shorter than 4 x the particle count");
-    const void *columns[8] = {};
-    bool is_f32 = false;
-    if (particle_columns(ctx, keys, 7, count, columns, is_f32, "a moment profile")) return 1;
-    double *label = nullptr, *values = nullptr;
-    if (fp64_columns(ctx, "a moment profile's label", {label_key}, count, &label) ||
-        fp64_columns(ctx, "a moment profile's values (4 per particle)", {values_key}, count*moment_count, &values)) {
-        return 1;
-    }
-    if (enter(ctx)) return 1;
-    gfhip::launch_moment_values(columns, is_f32, count, p->map, p->field, p->packed.get(), p->fpol.get(), label, values, ctx->stream);
-    GFHIP_TRY(ctx, hipGetLastError(), "moment values launch");
-    return 0;
-}
-
-extern "C" int gfhip_moments_counts(gfhip_moments *p, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    return p ? p->counts(samples, outside, skipped) : 1;
-}
-
-extern "C" int gfhip_moments_state(gfhip_moments *p, int64_t *limbs) {
-    if (!p) return 1;
-    if (!limbs) return p->ctx->fail("gfhip_moments_state needs a destination");
-    return p->state_to(limbs);
-}
-
-extern "C" int gfhip_moments_merge(gfhip_moments *p, const int64_t *limbs, size_t ns, size_t nm, uint64_t samples,
-                                   uint64_t outside, uint64_t skipped) {
-    if (!p) return 1;
-    if (!limbs) return p->ctx->fail("gfhip_moments_merge needs a state");
-    if (p->batches || ns != p->ns || nm != moment_count) return p->ctx->fail("merge: a moment profile of another shape");
-    return p->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_moments_merge_batches(gfhip_moments *p, const int64_t *limbs, size_t batches, size_t ns, size_t nm,
-                                           uint64_t samples, uint64_t outside, uint64_t skipped) {
-    if (!p) return 1;
-    if (!limbs) return p->ctx->fail("gfhip_moments_merge_batches needs a state");
-    if (!p->batches || batches != p->batches || ns != p->ns || nm != moment_count) {
-        return p->ctx->fail("merge: a moment profile of another shape");
-    }
-    return p->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_moments_read(gfhip_moments *p, double divisor, double *values) {
-    if (!p) return 1;
-    if (!values) return p->ctx->fail("gfhip_moments_read needs a destination");
-    return p->read(divisor, values);
-}
-
-//  Not through enter(): as gfhip_flux_info.
-extern "C" int gfhip_moments_info(gfhip_moments *p, struct gfhip_flux_info *info) {
-    if (!p) return 1;
-    if (!info) return p->ctx->fail("gfhip_moments_info needs a destination");
-    p->info_to(info);
-    return 0;
-}
-
-//  The map, the field and the tables of a host call, or why they are refused.
-static const char *moments_host_of(const gfhip_flux_map *map, const gfhip_spectrum_field *field, gfhip::flux::map &m,
-                                   gfhip::flux::field &f, gfhip::moments::host_tables &t) {
-    if (const char *refused = flux_map_of(map, m)) return refused;
-    if (const char *refused = phase_field_of(field, f)) return refused;
-    t.coefficients = map->coefficients;
-    t.table = static_cast<size_t> (map->numr*map->numz);
-    for (size_t k = 0; k < 4; k++) t.fpol[k] = field->fpol[k];
-    return nullptr;
-}
-
-//  Host side, no device: flux_label.hpp on the caller's 16 + 4 tables (moments_host.hpp).
-extern "C" int gfhip_moments_values_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const void *const columns[7],
-                                         int is_f32, size_t count, double *label, double *values) {
-    bool complete = map && field && columns && ((label && values) || !count);
-    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
-    if (!complete) {
-        creation_error = "gfhip_moments_values_host needs a map, a field, seven columns and two destinations";
-        return 1;
-    }
-    gfhip::flux::map m;
-    gfhip::flux::field f;
-    gfhip::moments::host_tables t;
-    if (const char *refused = moments_host_of(map, field, m, f, t)) {
-        creation_error = refused;
-        return 1;
-    }
-    if (is_f32) {
-        gfhip::moments::values_host<float> (m, f, t, columns, count, label, values);
-    } else {
-        gfhip::moments::values_host<double> (m, f, t, columns, count, label, values);
-    }
-    return 0;
-}
-
-extern "C" int gfhip_moments_add_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *sedges, size_t ns,
-                                      const void *const columns[8], int is_f32, size_t count, int64_t *limbs, uint64_t counters[3]) {
-    bool complete = map && field && sedges && columns && limbs && counters;
-    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
-    if (!complete) {
-        creation_error = "gfhip_moments_add_host needs a map, a field, the label edges, seven columns, limbs and counters";
-        return 1;
-    }
-    gfhip::flux::map m;
-    gfhip::flux::field f;
-    gfhip::moments::host_tables t;
-    const char *refused = moments_axis_of(sedges, ns);
-    if (!refused) refused = moments_host_of(map, field, m, f, t);
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    if (is_f32) {
-        gfhip::moments::add_host<float> (m, f, t, sedges, ns, columns, count, limbs, counters);
-    } else {
-        gfhip::moments::add_host<double> (m, f, t, sedges, ns, columns, count, limbs, counters);
-    }
-    return 0;
-}
-
-//  The batches and the particle range of a host call, or why they are refused.
-static const char *host_batches_refused(const size_t batches, const uint64_t first_particle, const size_t count) {
-    if (batches < 1 || batches > gfhip::batches::max_batches) return "a batched object has 1 to 256 batches";
-    if (first_particle + static_cast<uint64_t> (count) < first_particle) return "first_particle + count overflows 64 bits";
-    return nullptr;
-}
-
-//  limbs: [batches][ns][4][67] (moments_host.hpp's add_particles_host).
-extern "C" int gfhip_moments_add_particles_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *sedges,
-                                                size_t ns, size_t batches, const void *const columns[8], int is_f32, size_t count,
-                                                uint64_t first_particle, int64_t *limbs, uint64_t counters[3]) {
-    bool complete = map && field && sedges && columns && limbs && counters;
-    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
-    if (!complete) {
-        creation_error = "gfhip_moments_add_particles_host needs a map, a field, the label edges, seven columns, limbs and counters";
-        return 1;
-    }
-    gfhip::flux::map m;
-    gfhip::flux::field f;
-    gfhip::moments::host_tables t;
-    const char *refused = moments_axis_of(sedges, ns);
-    if (!refused) refused = host_batches_refused(batches, first_particle, count);
-    if (!refused) refused = moments_host_of(map, field, m, f, t);
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    if (is_f32) {
-        gfhip::moments::add_particles_host<float> (m, f, t, sedges, ns, static_cast<unsigned int> (batches), first_particle, columns,
-                                                   count, limbs, counters);
-    } else {
-        gfhip::moments::add_particles_host<double> (m, f, t, sedges, ns, static_cast<unsigned int> (batches), first_particle,
-                                                    columns, count, limbs, counters);
-    }
-    return 0;
-}
-
-//  limbs: [batches][ns][np][ng][67] (phase_host.hpp's add_particles_host).
-extern "C" int gfhip_phase_add_particles_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double *sedges,
-                                              size_t ns, const double *pedges, size_t np, const double *gedges, size_t ng,
-                                              size_t batches, const void *const columns[8], int is_f32, size_t count,
-                                              uint64_t first_particle, int64_t *limbs, uint64_t counters[3]) {
-    bool complete = map && field && sedges && pedges && gedges && columns && limbs && counters;
-    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
-    if (!complete) {
-        creation_error = "gfhip_phase_add_particles_host needs a map, a field, three edge arrays, seven columns, limbs and counters";
-        return 1;
-    }
-    const double *axes[3] = {sedges, pedges, gedges};
-    const size_t n[3] = {ns, np, ng};
-    gfhip::flux::map m;
-    gfhip::flux::field f;
-    gfhip::moments::host_tables t;
-    const char *refused = nullptr;
-    size_t cells = 1;
-    for (int a = 0; !refused && a < 3; a++) {
-        if (n[a] < 1 || n[a] > flux_cell_limit) {
-            refused = "a distribution has 1 to 4096 cells per axis (at least two edges)";
-        } else if (!edges_increase(axes[a], n[a])) {
-            refused = "the edges of a distribution must be finite and strictly increasing";
-        }
-        cells *= n[a];
-    }
-    if (!refused && cells > phase_cell_limit) refused = "a distribution has at most 2^20 cells (536 B each)";
-    if (!refused) refused = host_batches_refused(batches, first_particle, count);
-    if (!refused) refused = moments_host_of(map, field, m, f, t);
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    if (is_f32) {
-        gfhip::phase::add_particles_host<float> (m, f, t, axes, n, static_cast<unsigned int> (batches), first_particle, columns,
-                                                 count, limbs, counters);
-    } else {
-        gfhip::phase::add_particles_host<double> (m, f, t, axes, n, static_cast<unsigned int> (batches), first_particle, columns,
-                                                  count, limbs, counters);
-    }
-    return 0;
-}
-
-//  First-exit trackers (confinement.hip, flux_label.hpp).  The axes and the cells are a distribution's; deposits always
-//  go to the global state, so the launch shape is the global path's whatever the map's flags say.
-
-//  The three axes of a footprint checked and laid one after the other, or why they are refused.
-static const char *confine_axes_of(const double *const *axes, const size_t *n, std::vector<double> &edges, size_t &cells) {
-    cells = 1;
-    for (int a = 0; a < 3; a++) {
-        if (n[a] < 1 || n[a] > flux_cell_limit) return "a loss footprint has 1 to 4096 cells per axis (at least two edges)";
-        if (!edges_increase(axes[a], n[a])) return "the edges of a loss footprint must be finite and strictly increasing";
-        edges.insert(edges.end(), axes[a], axes[a] + n[a] + 1);
-        cells *= n[a];                                 // at most 2^36
-    }
-    if (cells > phase_cell_limit) return "a loss footprint has at most 2^20 cells (536 B each)";
-    return nullptr;
-}
-
-extern "C" gfhip_confine *gfhip_confine_create(gfhip_context *ctx, const gfhip_flux_map *map, double limit, const double *redges,
-                                               size_t nr, const double *zedges, size_t nz, const double *gedges, size_t ng,
-                                               size_t count, int is_f32, uint64_t alive_key, size_t capacity) {
-    if (!ctx) return nullptr;
-    if (!map || !redges || !zedges || !gedges) {
-        ctx->fail("a confinement tracker needs a map and three edge arrays");
-        return nullptr;
-    }
-    const double *axes[3] = {redges, zedges, gedges};
-    const size_t n[3] = {nr, nz, ng};
-    std::vector<double> edges;
-    size_t cells = 0;
-    if (const char *refused = confine_axes_of(axes, n, edges, cells)) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    if (limit != limit) {
-        ctx->fail("the limit of a confinement tracker must not be NaN");
-        return nullptr;
-    }
-    if (count == 0 || capacity == 0) {
-        ctx->fail("a confinement tracker needs at least one particle and room for at least one check");
-        return nullptr;
-    }
-    gfhip_flux_map global = *map;
-    global.flags |= gfhip::flux::flag_no_private_sums;
-    std::unique_ptr<gfhip_confine> c(new gfhip_confine);
-    c->limit = limit;
-    c->count = count;
-    c->capacity = capacity;
-    c->is_f32 = is_f32 != 0;
-    c->alive_key = alive_key;
-    for (int a = 0; a < 3; a++) {
-        c->n[a] = n[a];
-        c->scale[a] = static_cast<double> (n[a])/(axes[a][n[a]] - axes[a][0]);
-    }
-    if (c->create(ctx, &global, cells, edges, nullptr) || enter(ctx) ||
-        ensure_buffer(ctx, alive_key, count, c->is_f32 ? GFIR_F32 : GFIR_F64, nullptr) ||
-        ctx->check(allocate(c->lost_step, count*sizeof(uint32_t)), "hipMalloc(lost steps)") ||
-        ctx->check(allocate(c->newly_lost, capacity*sizeof(unsigned long long)), "hipMalloc(newly lost)") ||
-        ctx->check(hipMemsetAsync(c->newly_lost.get(), 0, capacity*sizeof(unsigned long long), ctx->stream), "hipMemset(newly lost)")) {
-        return nullptr;
-    }
-    gfhip::launch_confinement_reset(count, c->lost_step.get(), find_buffer(ctx, alive_key)->pointer, c->is_f32, nullptr, nullptr,
-                                    ctx->stream);
-    if (ctx->check(hipGetLastError(), "confinement reset launch")) return nullptr;
-    ctx->confines.push_back(std::move(c));
-    return ctx->confines.back().get();
-}
-
-extern "C" void gfhip_confine_destroy(gfhip_confine *c) {
-    destroy_in(&gfhip_context::confines, c);
-}
-
-extern "C" int gfhip_confine_check(gfhip_confine *c, const uint64_t keys[7], uint64_t weight_key, int has_weight,
-                                   uint64_t exit_r_key, uint64_t exit_z_key, int has_exit, uint32_t step) {
-    if (!c) return 1;
-    gfhip_context *ctx = c->ctx;
-    if (!keys) return ctx->fail("gfhip_confine_check needs its 7 keys");
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], weight_key};
-    const void *columns[8] = {};
-    bool is_f32 = false;
-    if (particle_columns(ctx, all, has_weight ? 8 : 7, c->count, columns, is_f32, "a confinement tracker")) return 1;
-    if (is_f32 != c->is_f32) return ctx->fail("the columns are not of the confinement tracker's type");
-    const buffer *alive = find_buffer(ctx, c->alive_key);
-    if (!alive) return 1;
-    if (alive->dtype != (c->is_f32 ? GFIR_F32 : GFIR_F64) || alive->count < c->count) {
-        return ctx->fail("the alive buffer of a confinement tracker has been replaced by one of another type or length");
-    }
-    double *exits[2] = {nullptr, nullptr};
-    if (has_exit && fp64_columns(ctx, "a confinement tracker's exit", {exit_r_key, exit_z_key}, c->count, exits)) return 1;
-    if (step == GFHIP_CONFINED) return ctx->fail("step 0xFFFFFFFF means confined: a check cannot have it");
-    if (!c->steps.empty() && step < c->steps.back()) return ctx->fail("a check's step is below the previous check's");
-    if (c->steps.size() >= c->capacity) return ctx->fail("more checks than the confinement tracker's capacity");
-    if (enter(ctx)) return 1;
-    if (has_exit && !(c->exit_ready && c->exit_keys[0] == exit_r_key && c->exit_keys[1] == exit_z_key)) {
-        gfhip::launch_confinement_reset(c->count, nullptr, nullptr, c->is_f32, exits[0], exits[1], ctx->stream);
-        GFHIP_TRY(ctx, hipGetLastError(), "confinement reset launch");
-        c->exit_ready = true;
-        c->exit_keys[0] = exit_r_key;
-        c->exit_keys[1] = exit_z_key;
-    }
-    unsigned long long *entry = c->newly_lost.get() + c->steps.size();
-    if (c->add(c->count, [&](const size_t first, const size_t piece) {
-            gfhip::launch_confinement_check(columns, alive->pointer, c->is_f32, first, piece, c->map, c->packed.get(), c->limit,
-                                            c->edges.get(), c->n, c->scale, step, c->lost_step.get(), exits[0], exits[1], entry,
-                                            c->block, c->max_workgroups, c->lds_bytes, c->state.get(), c->counters.get(),
-                                            ctx->stream);
-        })) {
-        return 1;
-    }
-    c->steps.push_back(step);
-    return 0;
-}
-
-extern "C" int gfhip_confine_lost_steps(gfhip_confine *c, uint32_t *lost_step) {
-    if (!c) return 1;
-    gfhip_context *ctx = c->ctx;
-    if (!lost_step) return ctx->fail("gfhip_confine_lost_steps needs a destination");
-    if (enter(ctx)) return 1;
-    GFHIP_TRY(ctx, hipMemcpyAsync(lost_step, c->lost_step.get(), c->count*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpyAsync(lost steps)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return 0;
-}
-
-extern "C" int gfhip_confine_history(gfhip_confine *c, uint32_t *steps, uint64_t *newly_lost, size_t *checks) {
-    if (!c) return 1;
-    gfhip_context *ctx = c->ctx;
-    if (!checks) return ctx->fail("gfhip_confine_history needs a destination for the number of checks");
-    *checks = c->steps.size();
-    if (steps) std::copy(c->steps.begin(), c->steps.end(), steps);
-    if (newly_lost && !c->steps.empty()) {
-        if (enter(ctx)) return 1;
-        GFHIP_TRY(ctx, hipMemcpyAsync(newly_lost, c->newly_lost.get(), c->steps.size()*sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                      ctx->stream), "hipMemcpyAsync(newly lost)");
-        GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    return 0;
-}
-
-extern "C" int gfhip_confine_counts(gfhip_confine *c, uint64_t *samples, uint64_t *outside, uint64_t *skipped) {
-    return c ? c->counts(samples, outside, skipped) : 1;
-}
-
-extern "C" int gfhip_confine_state(gfhip_confine *c, int64_t *limbs) {
-    if (!c) return 1;
-    if (!limbs) return c->ctx->fail("gfhip_confine_state needs a destination");
-    return c->state_to(limbs);
-}
-
-extern "C" int gfhip_confine_merge(gfhip_confine *c, const int64_t *limbs, size_t nr, size_t nz, size_t ng, uint64_t samples,
-                                   uint64_t outside, uint64_t skipped) {
-    if (!c) return 1;
-    if (!limbs) return c->ctx->fail("gfhip_confine_merge needs a state");
-    if (nr != c->n[0] || nz != c->n[1] || ng != c->n[2]) return c->ctx->fail("merge: a loss footprint of another shape");
-    return c->merge(limbs, samples, outside, skipped);
-}
-
-extern "C" int gfhip_confine_read(gfhip_confine *c, double divisor, double *values) {
-    if (!c) return 1;
-    if (!values) return c->ctx->fail("gfhip_confine_read needs a destination");
-    return c->read(divisor, values);
-}
-
-//  Not through enter(): as gfhip_flux_info.
-extern "C" int gfhip_confine_info(gfhip_confine *c, struct gfhip_flux_info *info) {
-    if (!c) return 1;
-    if (!info) return c->ctx->fail("gfhip_confine_info needs a destination");
-    c->info_to(info);
-    return 0;
-}
-
-extern "C" int gfhip_confine_check_host(const gfhip_flux_map *map, double limit, const double *redges, size_t nr,
-                                        const double *zedges, size_t nz, const double *gedges, size_t ng,
-                                        const void *const columns[8], int is_f32, size_t count, uint32_t step, uint32_t *lost_step,
-                                        void *alive, double *exit_r, double *exit_z, uint64_t *newly_lost, int64_t *limbs,
-                                        uint64_t counters[3]) {
-    bool complete = map && columns && newly_lost && ((lost_step && alive) || !count) && !exit_r == !exit_z &&
-                    (!limbs || (redges && zedges && gedges && counters));
-    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count || (k >= 3 && k <= 5) || (k == 6 && !limbs);
-    if (!complete) {
-        creation_error = "gfhip_confine_check_host needs a map, the columns x, y, z and gamma, lost_step, alive and newly_lost, "
-                         "both exit arrays or neither, and with limbs the three edge arrays and the counters";
-        return 1;
-    }
-    gfhip::flux::map m;
-    const double *axes[3] = {redges, zedges, gedges};
-    const size_t n[3] = {nr, nz, ng};
-    std::vector<double> edges;
-    size_t cells = 0;
-    const char *refused = flux_map_of(map, m);
-    if (!refused && limbs) refused = confine_axes_of(axes, n, edges, cells);
-    if (!refused && limit != limit) refused = "the limit of a confinement tracker must not be NaN";
-    if (!refused && step == GFHIP_CONFINED) refused = "step 0xFFFFFFFF means confined: a check cannot have it";
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    const size_t table = static_cast<size_t> (map->numr*map->numz);
-    if (is_f32) {
-        gfhip::confine::check_host<float> (m, map->coefficients, table, limit, axes, n, columns, count, step, lost_step, static_cast<float *> (alive), exit_r,
-                                   exit_z, newly_lost, limbs, counters);
-    } else {
-        gfhip::confine::check_host<double> (m, map->coefficients, table, limit, axes, n, columns, count, step, lost_step, static_cast<double *> (alive), exit_r,
-                                    exit_z, newly_lost, limbs, counters);
-    }
-    return 0;
-}
-
-//  Particle sources (particle_source.hip, particle_draw.hpp).
-
-//  The route of a source made with neither route flag.
-static const bool source_refill_by_default = true;
-
-//  What the rule needs beside the map and the field, or why a source is refused.
-static const char *source_parameters_of(const double *box, const double slo, const double shi, const double blo, const double bhi,
-                                        const double xlo, const double xhi, const double *sedges, const double *accept,
-                                        const size_t ns, const uint64_t seed, const uint32_t attempts, const uint32_t flags,
-                                        gfhip::draw::parameters &par) {
-    if (!box) return "a particle source needs its box {rlo, rhi, zlo, zhi}";
-    for (int k = 0; k < 4; k++) {
-        if (!std::isfinite(box[k])) return "the box of a particle source must be finite";
-    }
-    if (!(box[0] < box[1]) || !(box[2] < box[3]) || box[0] < 0.0) return "the box of a particle source needs 0 <= rlo < rhi and zlo < zhi";
-    if (!(slo < shi)) return "the label range of a particle source must not be empty or NaN";
-    if (!(blo < bhi) || !(blo >= 0.0) || !(bhi < 1.0)) return "the speed range of a particle source needs 0 <= blo < bhi < 1";
-    if (!(xlo < xhi) || !(xlo >= -1.0) || !(xhi <= 1.0)) return "the pitch range of a particle source needs -1 <= xlo < xhi <= 1";
-    if (attempts == 0 || attempts > gfhip::draw::max_attempts) return "a particle source makes 1 to 4096 attempts";
-    if (ns > static_cast<size_t> (gfhip::draw::max_profile_cells)) return "the profile of a particle source has at most 256 cells";
-    if ((ns != 0) != (sedges != nullptr) || (ns != 0) != (accept != nullptr)) {
-        return "the profile of a particle source is ns + 1 edges and ns probabilities, or neither with ns = 0";
-    }
-    if (ns && !edges_increase(sedges, ns)) return "the edges of a particle source's profile must be finite and strictly increasing";
-    for (size_t k = 0; k < ns; k++) {
-        if (!(accept[k] >= 0.0 && accept[k] <= 1.0)) return "the probabilities of a particle source's profile lie in [0, 1]";
-    }
-    if (flags & ~gfhip::draw::known_flags) return "unknown flag bits for a particle source";
-    if ((flags & gfhip::draw::known_flags) == gfhip::draw::known_flags) return "a particle source takes one route, plain or refill";
-    par = gfhip::draw::parameters_of(box, slo, shi, blo, bhi, xlo, xhi, seed, attempts, static_cast<int> (ns));
-    return nullptr;
-}
-
-extern "C" gfhip_source *gfhip_source_create(gfhip_context *ctx, const gfhip_flux_map *map, const gfhip_spectrum_field *field,
-                                             const double box[4], double slo, double shi, double blo, double bhi, double xlo,
-                                             double xhi, const double *sedges, const double *accept, size_t ns, uint64_t seed,
-                                             uint32_t attempts, int is_f32, uint32_t flags, size_t max_workgroups) {
-    if (!ctx) return nullptr;
-    if (!map || !field) {
-        ctx->fail("a particle source needs a map and a field");
-        return nullptr;
-    }
-    std::unique_ptr<gfhip_source> s(new gfhip_source);
-    const char *refused = flux_map_of(map, s->map);
-    if (!refused) refused = phase_field_of(field, s->field);
-    if (!refused) refused = source_parameters_of(box, slo, shi, blo, bhi, xlo, xhi, sedges, accept, ns, seed, attempts, flags, s->par);
-    if (refused) {
-        ctx->fail(refused);
-        return nullptr;
-    }
-    s->ctx = ctx;
-    s->is_f32 = is_f32 != 0;
-    s->refill = flags & gfhip::draw::known_flags ? (flags & gfhip::draw::flag_refill) != 0 : source_refill_by_default;
-    s->max_workgroups = max_workgroups ? max_workgroups : static_cast<size_t> (ctx->num_cus)*8u;
-    std::vector<double> lines, cubics, profile(1, 0.0);
-    if (!psi_lines(map, lines) || !fpol_lines(field, cubics)) {
-        ctx->fail("a particle source's tables do not fit the host's memory");
-        return nullptr;
-    }
-    if (ns) {
-        profile.assign(sedges, sedges + ns + 1);
-        profile.insert(profile.end(), accept, accept + ns);
-        s->scale = static_cast<double> (ns)/(sedges[ns] - sedges[0]);
-    }
-    if (enter(ctx) ||
-        ctx->check(allocate(s->packed, lines.size()*sizeof(double)), "hipMalloc(flux tables)") ||
-        ctx->check(hipMemcpy(s->packed.get(), lines.data(), lines.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(flux tables)") ||
-        ctx->check(allocate(s->fpol, cubics.size()*sizeof(double)), "hipMalloc(fpol tables)") ||
-        ctx->check(hipMemcpy(s->fpol.get(), cubics.data(), cubics.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fpol tables)") ||
-        ctx->check(allocate(s->profile, profile.size()*sizeof(double)), "hipMalloc(profile)") ||
-        ctx->check(hipMemcpy(s->profile.get(), profile.data(), profile.size()*sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(profile)") ||
-        ctx->check(allocate(s->counters, 4*sizeof(unsigned long long)), "hipMalloc(counters)") ||
-        ctx->check(hipMemsetAsync(s->counters.get(), 0, 4*sizeof(unsigned long long), ctx->stream), "hipMemset(counters)") ||
-        ctx->check(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
-        return nullptr;
-    }
-    ctx->sources.push_back(std::move(s));
-    return ctx->sources.back().get();
-}
-
-extern "C" void gfhip_source_destroy(gfhip_source *s) {
-    destroy_in(&gfhip_context::sources, s);
-}
-
-extern "C" int gfhip_source_fill(gfhip_source *s, const uint64_t keys[7], uint64_t placed_key, int has_placed,
-                                 uint64_t first_particle, size_t count) {
-    if (!s) return 1;
-    gfhip_context *ctx = s->ctx;
-    if (!keys) return ctx->fail("gfhip_source_fill needs its 7 keys");
-    if (count == 0) return ctx->fail("a particle source fills at least one particle");
-    if (first_particle + static_cast<uint64_t> (count) < first_particle) return ctx->fail("first_particle + count overflows 64 bits");
-    const uint64_t all[8] = {keys[0], keys[1], keys[2], keys[3], keys[4], keys[5], keys[6], placed_key};
-    const size_t used = has_placed ? 8 : 7;
-    const uint32_t dtype = s->is_f32 ? GFIR_F32 : GFIR_F64;
-//  Everything is looked at before anything is allocated.
-    for (size_t c = 0; c < used; c++) {
-        for (size_t other = 0; other < c; other++) {
-            if (all[other] == all[c]) return ctx->fail("a particle source fills eight different buffers: a key is given twice");
-        }
-        const auto found = ctx->buffers.find(all[c]);
-        if (found == ctx->buffers.end()) continue;
-        if (found->second.dtype != dtype) return ctx->fail("a buffer is not of the particle source's type");
-        if (found->second.count < count) return ctx->fail("a particle source's buffer is shorter than the particle count");
-    }
-    if (enter(ctx)) return 1;
-    void *columns[8] = {};
-    for (size_t c = 0; c < used; c++) {
-        if (ensure_buffer(ctx, all[c], count, dtype, nullptr)) return 1;
-        columns[c] = find_buffer(ctx, all[c])->pointer;
-    }
-    gfhip::launch_particle_source(columns, columns[7], s->is_f32, count, first_particle, s->map, s->field, s->par, s->packed.get(),
-                                  s->fpol.get(), s->profile.get(), s->scale, s->refill, s->max_workgroups, s->counters.get(),
-                                  ctx->stream);
-    return ctx->check(hipGetLastError(), "particle source launch");
-}
-
-extern "C" int gfhip_source_counts(gfhip_source *s, uint64_t counters[4]) {
-    if (!s) return 1;
-    gfhip_context *ctx = s->ctx;
-    if (!counters) return ctx->fail("gfhip_source_counts needs a destination");
-    if (enter(ctx)) return 1;
-    unsigned long long host[4] = {0, 0, 0, 0};
-    GFHIP_TRY(ctx, hipMemcpyAsync(host, s->counters.get(), sizeof(host), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(counters)");
-    GFHIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    for (int k = 0; k < 4; k++) counters[k] = host[k];
-    return 0;
-}
-
-//  Not through enter(): as gfhip_flux_info.
-extern "C" int gfhip_source_info(gfhip_source *s, struct gfhip_flux_info *info) {
-    if (!s) return 1;
-    if (!info) return s->ctx->fail("gfhip_source_info needs a destination");
-    info->private_sums = s->refill ? 1u : 0u;
-    info->workgroup_size = 256;
-    info->cap_cells = 0;
-    info->max_workgroups = s->max_workgroups;
-    info->lds_bytes = s->par.ns ? (2*static_cast<size_t> (s->par.ns) + 1)*sizeof(double) : 0;
-    return 0;
-}
-
-extern "C" int gfhip_source_fill_host(const gfhip_flux_map *map, const gfhip_spectrum_field *field, const double box[4], double slo,
-                                      double shi, double blo, double bhi, double xlo, double xhi, const double *sedges,
-                                      const double *accept, size_t ns, uint64_t seed, uint32_t attempts, uint32_t flags,
-                                      void *const columns[8], int is_f32, uint64_t first_particle, size_t count,
-                                      uint64_t counters[4]) {
-    bool complete = map && field && columns && counters;
-    for (int k = 0; complete && k < 7; k++) complete = columns[k] || !count;
-    if (!complete) {
-        creation_error = "gfhip_source_fill_host needs a map, a field, the seven columns and the counters";
-        return 1;
-    }
-    gfhip::flux::map m;
-    gfhip::flux::field f;
-    gfhip::draw::parameters par;
-    const char *refused = flux_map_of(map, m);
-    if (!refused) refused = phase_field_of(field, f);
-    if (!refused) refused = source_parameters_of(box, slo, shi, blo, bhi, xlo, xhi, sedges, accept, ns, seed, attempts, flags, par);
-    if (!refused && first_particle + static_cast<uint64_t> (count) < first_particle) refused = "first_particle + count overflows 64 bits";
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    const gfhip::draw::host_tables tables = {map->coefficients, static_cast<size_t> (map->numr*map->numz),
-                                             {field->fpol[0], field->fpol[1], field->fpol[2], field->fpol[3]}, sedges, accept, ns};
-    if (is_f32) {
-        gfhip::draw::fill_host<float> (m, f, par, tables, columns, columns[7], first_particle, count, counters);
-    } else {
-        gfhip::draw::fill_host<double> (m, f, par, tables, columns, columns[7], first_particle, count, counters);
-    }
-    return 0;
-}
-
-extern "C" void gfhip_source_block_host(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
-    gfhip::draw::philox(counter, key, out);
-}
-
-//  What a run of quadrature points needs beside the map (flux_label.hpp), or why it is refused.
-struct volume_points {
-    unsigned long long row = 0;                        // numz*sub: the sub-cells along z
-    double twice_sub = 0.0, area = 0.0;
-    gfhip::flux::window window = {};
-};
-
-static const char *volume_points_of(const gfhip::flux::map &m, const uint32_t sub, const gfhip_flux_window *window,
-                                    const uint64_t first, const uint64_t count, volume_points &p) {
-    if (sub < 1 || sub > 256) return "flux volumes: sub must be 1 to 256";
-    if (!(m.dr > 0.0) || !(m.dz > 0.0) || !(m.rmin >= 0.0)) return "flux volumes need a map with dr > 0, dz > 0 and rmin >= 0";
-//  numr*numz <= 2^31 and sub*sub <= 2^16: the total fits 64 bits with room to spare.
-    p.row = m.columns*sub;
-    const uint64_t total = static_cast<uint64_t> (m.numr)*sub*p.row;
-    if (first + count < first || first + count > total) return "flux volumes: first + count exceeds the numr*sub*numz*sub points of the map";
-    const double inf = std::numeric_limits<double>::infinity();
-    p.window = window ? gfhip::flux::window{window->rlo, window->rhi, window->zlo, window->zhi} : gfhip::flux::window{-inf, inf, -inf, inf};
-    if (!(p.window.rlo < p.window.rhi) || !(p.window.zlo < p.window.zhi)) return "flux volumes: a window needs rlo < rhi and zlo < zhi, no NaN";
-    p.twice_sub = static_cast<double> (2u*sub);
-    p.area = gfhip::flux::sub_area(m, sub);
-    return nullptr;
-}
-
-extern "C" int gfhip_flux_add_volumes(gfhip_flux *f, uint32_t sub, const gfhip_flux_window *window, uint64_t first, uint64_t count) {
-    if (!f) return 1;
-    if (f->batches) return f->ctx->fail("flux volumes have no rays: a batched flux profile does not take them");
-    volume_points p;
-    if (const char *refused = volume_points_of(f->map, sub, window, first, count, p)) return f->ctx->fail(refused);
-    return f->add(count, [&](const size_t done, const size_t piece) {
-        gfhip::launch_flux_volumes(first + done, piece, p.row, p.twice_sub, p.area, p.window, f->map, f->packed.get(),
-                                   f->edges.get(), f->cells, f->scale, f->is_private, f->block, f->max_workgroups,
-                                   f->lds_bytes, f->state.get(), f->counters.get(), f->ctx->stream);
-    });
-}
-
-//  Host side, no device: the quadrature and the label of flux_label.hpp and superacc.hpp's deposit on the CPU.
-extern "C" int gfhip_flux_volumes_host(const gfhip_flux_map *map, const double *edges, size_t cells, uint32_t sub,
-                                       const gfhip_flux_window *window, uint64_t first, uint64_t count,
-                                       int64_t *limbs, uint64_t counters[3]) {
-    if (!map || !edges || !limbs || !counters) {
-        creation_error = "gfhip_flux_volumes_host needs a map, edges, limbs and counters";
-        return 1;
-    }
-    if (cells < 1 || cells > flux_cell_limit) {
-        creation_error = "a flux profile has 1 to 4096 cells";
-        return 1;
-    }
-    if (!edges_increase(edges, cells)) {
-        creation_error = "the edges of a flux profile must be finite and strictly increasing";
-        return 1;
-    }
-    gfhip::flux::map m;
-    volume_points p;
-    const char *refused = flux_map_of(map, m);
-    if (!refused) refused = volume_points_of(m, sub, window, first, count, p);
-    if (refused) {
-        creation_error = refused;
-        return 1;
-    }
-    const size_t table = static_cast<size_t> (map->numr*map->numz);
-    const auto normalise_all = [&]() {
-        for (size_t cell = 0; cell < cells; cell++) gfhip::superacc::normalise(limbs + cell*gfhip::superacc::limbs);
-    };
-    uint64_t pending = 0, outside = 0, skipped = 0;
-    unsigned long long gr = first/p.row, gz = first%p.row;
-    for (uint64_t t = 0; t < count; t++) {
-        const double r = gfhip::flux::sub_centre(m.rmin, m.dr, gr, p.twice_sub);
-        const double z = gfhip::flux::sub_centre(m.zmin, m.dz, gz, p.twice_sub);
-        if (++gz == p.row) {
-            gz = 0;
-            gr++;
-        }
-        double tr, tz, c[16];
-        const long long at = gfhip::flux::in_window(p.window, r, z) ? gfhip::flux::locate(m, r, 0.0, z, tr, tz) : -1;
-        if (at < 0) {
-            outside++;
-            continue;
-        }
-        for (size_t k = 0; k < 16; k++) c[k] = map->coefficients[k*table + static_cast<size_t> (at)];
-        const double label = gfhip::flux::label_of(m, gfhip::flux::psi_of(c, tr, tz));
-        if (!(label >= edges[0] && label < edges[cells])) {
-            outside++;
-            continue;
-        }
-        const size_t cell = static_cast<size_t> (std::upper_bound(edges, edges + cells + 1, label) - edges) - 1;
-        const double w = gfhip::flux::sub_weight(r, p.area);
-        if (!gfhip::superacc::is_finite(w)) {
-            skipped++;
-            continue;
-        }
-        if (++pending > gfhip::superacc::deposits_per_normalise) {
-            normalise_all();
-            pending = 1;
-        }
-        gfhip::superacc::deposit(limbs + cell*gfhip::superacc::limbs, w);
-    }
-    normalise_all();
-    counters[0] += count;
-    counters[1] += outside;
-    counters[2] += skipped;
-    return 0;
-}
-
-//  Host side, no device: the functions of superacc.hpp that the kernels run, on one accumulator.
-extern "C" int gfhip_exact_sum(const double *values, size_t count, double *sum, int64_t *limbs) {
-    if ((!values && count) || !sum) return 1;
-    int64_t acc[gfhip::superacc::limbs] = {0};
-    uint64_t pending = 0;
-    for (size_t i = 0; i < count; i++) {
-        if (!gfhip::superacc::is_finite(values[i])) {
-            creation_error = "gfhip_exact_sum takes finite values";
-            return 1;
-        }
-        if (++pending > gfhip::superacc::deposits_per_normalise) {
-            gfhip::superacc::normalise(acc);
-            pending = 1;
-        }
-        gfhip::superacc::deposit(acc, values[i]);
-    }
-    gfhip::superacc::normalise(acc);
-    *sum = gfhip::superacc::round(acc);
-    if (limbs) std::memcpy(limbs, acc, sizeof(acc));
     return 0;
 }

@@ -41,41 +41,41 @@ constexpr int moment_count = 4;
 constexpr size_t moment_cap_bytes = private_cap*bytes_per_cell + (private_cap/moment_count + 1)*sizeof(double);
 static_assert(moment_cap_bytes <= lds_per_workgroup, "the cap fits one workgroup's LDS");
 
-//  The label and the four moments of one particle, all NaN outside the map.  `fpol`: [interval][4], 32-byte aligned.
+//  The label and the four moments of one particle, all NaN outside the map.
 __device__ __forceinline__ double moments_at(const flux::map &m, const flux::field &f, const double *__restrict__ packed,
                                              const double *__restrict__ fpol, const double x, const double y, const double z,
                                              const double ux, const double uy, const double uz, const double gamma,
                                              double *moments) {
-    double tr, tz;
-    const long long at = flux::locate(m, x, y, z, tr, tz);
-    if (at < 0) {
+    field_point p;
+    if (!point_at(m, f, packed, fpol, x, y, z, p)) {
 #pragma unroll
         for (int k = 0; k < moment_count; k++) moments[k] = __builtin_nan("");
         return __builtin_nan("");
     }
-    double c[16];
-    coefficients_at(packed, at, c);
-    double gr, gz, tp;
-    const double psi = flux::psi_gradient(m, c, tr, tz, gr, gz);
-    const int q = flux::fpol_interval(f, psi, tp);
-    const double2 *line = reinterpret_cast<const double2 *> (fpol) + static_cast<size_t> (q)*2;
-    const double2 low = line[0], high = line[1];
-    const double cubic[4] = {low.x, low.y, high.x, high.y};
-    flux::moments_of(x, y, flux::radius_of(x, y), ux, uy, uz, gamma, gr, gz, flux::fpol_of(cubic, tp), moments);
-    return flux::canonical(flux::label_of(m, psi));
+    flux::moments_of(x, y, flux::radius_of(x, y), ux, uy, uz, gamma, p.gr, p.gz, p.fpol, moments);
+//  Not p.label: formed here, after the moments, the label is not held in registers across them (the kernels below need
+//  up to 12 fewer, one to two waves per SIMD more).
+    return flux::canonical(flux::label_of(m, p.psi));
+}
+
+//  The same of particle `at` of the columns, widened to fp64.
+template<typename T>
+__device__ __forceinline__ double moments_at(const flux::map &m, const flux::field &f, const double *__restrict__ packed,
+                                             const double *__restrict__ fpol, const particle_columns<T> &in,
+                                             const unsigned long long at, double *moments) {
+    return moments_at(m, f, packed, fpol, static_cast<double> (in.x[at]), static_cast<double> (in.y[at]),
+                      static_cast<double> (in.z[at]), static_cast<double> (in.ux[at]), static_cast<double> (in.uy[at]),
+                      static_cast<double> (in.uz[at]), static_cast<double> (in.gamma[at]), moments);
 }
 
 }  // namespace
 
-template<typename T>
-struct moment_columns {
-    const T *x, *y, *z, *ux, *uy, *uz, *gamma, *weight;    // weight: null when every particle has weight 1.0
-};
-
-//  counters: samples, outside, skipped, counted per particle.  edges: the ns + 1 of the label.
+//  counters: samples, outside, skipped, counted per particle.  edges: the ns + 1 of the label.  The loop is written out
+//  here: behind a shared loop function the four variants of this kernel need 2 to 10 registers more and lose a wave
+//  per SIMD each.
 template<bool PRIVATE, typename T>
 __global__ void __launch_bounds__(private_block)
-moment_deposit_kernel(const moment_columns<T> in, const unsigned long long count,
+moment_deposit_kernel(const particle_columns<T> in, const unsigned long long count,
                       const flux::map m, const flux::field f, const double *__restrict__ packed,
                       const double *__restrict__ fpol, const double *__restrict__ edges, const int ns, const double sscale,
                       unsigned long long *__restrict__ state, unsigned long long *__restrict__ counters) {
@@ -94,12 +94,9 @@ moment_deposit_kernel(const moment_columns<T> in, const unsigned long long count
         int is = -1;                                   // outside, as in the lanes past the end
         double v[moment_count] = {0.0, 0.0, 0.0, 0.0};
         if (present) {
-            const double w = in.weight ? static_cast<double> (in.weight[at]) : 1.0;
+            const double w = in.weight_of(at);
             double moments[moment_count];
-            const double label = moments_at(m, f, packed, fpol, static_cast<double> (in.x[at]), static_cast<double> (in.y[at]),
-                                            static_cast<double> (in.z[at]), static_cast<double> (in.ux[at]),
-                                            static_cast<double> (in.uy[at]), static_cast<double> (in.uz[at]),
-                                            static_cast<double> (in.gamma[at]), moments);
+            const double label = moments_at(m, f, packed, fpol, in, at, moments);
             is = deposit::find_cell(sedge, ns, sscale, label);
             flux::weighted_moments(w, moments, v);
         }
@@ -120,7 +117,7 @@ moment_deposit_kernel(const moment_columns<T> in, const unsigned long long count
 //  ONE batch of particles (ray_batches.hpp's rule, a particle in place of a ray) whatever the number of batches.
 template<bool PRIVATE, typename T>
 __global__ void __launch_bounds__(private_block)
-moment_deposit_particles_kernel(const moment_columns<T> in, const unsigned long long count, const unsigned long long first_particle,
+moment_deposit_particles_kernel(const particle_columns<T> in, const unsigned long long count, const unsigned long long first_particle,
                                 const unsigned int batch_count, const flux::map m, const flux::field f,
                                 const double *__restrict__ packed, const double *__restrict__ fpol,
                                 const double *__restrict__ edges, const int ns, const double sscale,
@@ -131,12 +128,9 @@ moment_deposit_particles_kernel(const moment_columns<T> in, const unsigned long 
     const double *sedge = sums.staged;
     deposit_batched_many<PRIVATE, moment_count> (sums, first_particle, count, batch_count, ns, state, counters,
                                                  [&](const uint64_t at, double *v, bool &finite) {
-        const double w = in.weight ? static_cast<double> (in.weight[at]) : 1.0;
+        const double w = in.weight_of(at);
         double moments[moment_count];
-        const double label = moments_at(m, f, packed, fpol, static_cast<double> (in.x[at]), static_cast<double> (in.y[at]),
-                                        static_cast<double> (in.z[at]), static_cast<double> (in.ux[at]),
-                                        static_cast<double> (in.uy[at]), static_cast<double> (in.uz[at]),
-                                        static_cast<double> (in.gamma[at]), moments);
+        const double label = moments_at(m, f, packed, fpol, in, at, moments);
         flux::weighted_moments(w, moments, v);
         finite = flux::moments_finite(v);
         return deposit::find_cell(sedge, ns, sscale, label);
@@ -146,124 +140,63 @@ moment_deposit_particles_kernel(const moment_columns<T> in, const unsigned long 
 //  One lane per particle: its label and its four moments, values[at*4 + k], NaN outside the map.
 template<typename T>
 __global__ void __launch_bounds__(256)
-moment_values_kernel(const moment_columns<T> in, const unsigned long long count, const flux::map m, const flux::field f,
+moment_values_kernel(const particle_columns<T> in, const unsigned long long count, const flux::map m, const flux::field f,
                      const double *__restrict__ packed, const double *__restrict__ fpol,
                      double *__restrict__ label, double *__restrict__ values) {
     const unsigned long long at = static_cast<unsigned long long> (blockIdx.x)*blockDim.x + threadIdx.x;
     if (at < count) {
         double moments[moment_count];
-        label[at] = moments_at(m, f, packed, fpol, static_cast<double> (in.x[at]), static_cast<double> (in.y[at]),
-                               static_cast<double> (in.z[at]), static_cast<double> (in.ux[at]), static_cast<double> (in.uy[at]),
-                               static_cast<double> (in.uz[at]), static_cast<double> (in.gamma[at]), moments);
+        label[at] = moments_at(m, f, packed, fpol, in, at, moments);
 #pragma unroll
         for (int k = 0; k < moment_count; k++) values[at*moment_count + k] = moments[k];
     }
 }
 
-//  Dynamic LDS above 64 KiB has to be asked for: always the cap's size, as flux_prepare does.
 hipError_t moments_prepare() {
-    for (const void *kernel : {reinterpret_cast<const void *> (&moment_deposit_kernel<true, float>),
-                               reinterpret_cast<const void *> (&moment_deposit_kernel<true, double>),
-                               reinterpret_cast<const void *> (&moment_deposit_particles_kernel<true, float>),
-                               reinterpret_cast<const void *> (&moment_deposit_particles_kernel<true, double>)}) {
-        const hipError_t status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      static_cast<int> (moment_cap_bytes));
-        if (status != hipSuccess) return status;
-    }
-    return hipSuccess;
+    return prepare_private({reinterpret_cast<const void *> (&moment_deposit_kernel<true, float>),
+                            reinterpret_cast<const void *> (&moment_deposit_kernel<true, double>),
+                            reinterpret_cast<const void *> (&moment_deposit_particles_kernel<true, float>),
+                            reinterpret_cast<const void *> (&moment_deposit_particles_kernel<true, double>)}, moment_cap_bytes);
 }
-
-namespace {
-
-template<typename T>
-moment_columns<T> columns_from(const void *const *columns, const size_t first, const bool with_weight) {
-    const T *const *typed = reinterpret_cast<const T *const *> (columns);
-    return {typed[0] + first, typed[1] + first, typed[2] + first, typed[3] + first, typed[4] + first, typed[5] + first,
-            typed[6] + first, with_weight ? typed[7] + first : nullptr};
-}
-
-template<typename T>
-void deposit_as(const void *const *columns, const size_t first, const size_t count, const flux::map &m, const flux::field &f,
-                const double *packed, const double *fpol, const double *edges, const size_t ns, const double sscale,
-                const bool is_private, const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
-                void *state, unsigned long long *counters, hipStream_t stream) {
-    const moment_columns<T> in = columns_from<T> (columns, first, columns[7] != nullptr);
-    const unsigned int grid = grid_of(count, block, max_workgroups);
-    if (is_private) {
-        hipLaunchKernelGGL((moment_deposit_kernel<true, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), m, f, packed, fpol, edges, static_cast<int> (ns), sscale,
-                           static_cast<unsigned long long *> (state), counters);
-    } else {
-        hipLaunchKernelGGL((moment_deposit_kernel<false, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), m, f, packed, fpol, edges, static_cast<int> (ns), sscale,
-                           static_cast<unsigned long long *> (state), counters);
-    }
-}
-
-template<typename T>
-void deposit_particles_as(const void *const *columns, const size_t first, const size_t count, const unsigned long long first_particle,
-                          const size_t batch_count, const flux::map &m, const flux::field &f, const double *packed,
-                          const double *fpol, const double *edges, const size_t ns, const double sscale, const bool is_private,
-                          const unsigned int block, const size_t max_workgroups, const size_t lds_bytes, void *state,
-                          unsigned long long *counters, hipStream_t stream) {
-    const moment_columns<T> in = columns_from<T> (columns, first, columns[7] != nullptr);
-    const unsigned int grid = batched_grid_of(count, block, max_workgroups, batch_count);
-    if (is_private) {
-        hipLaunchKernelGGL((moment_deposit_particles_kernel<true, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), first_particle, static_cast<unsigned int> (batch_count), m, f,
-                           packed, fpol, edges, static_cast<int> (ns), sscale, static_cast<unsigned long long *> (state), counters);
-    } else {
-        hipLaunchKernelGGL((moment_deposit_particles_kernel<false, T>), dim3(grid), dim3(block), lds_bytes, stream, in,
-                           static_cast<unsigned long long> (count), first_particle, static_cast<unsigned int> (batch_count), m, f,
-                           packed, fpol, edges, static_cast<int> (ns), sscale, static_cast<unsigned long long *> (state), counters);
-    }
-}
-
-}  // namespace
 
 void launch_moment_deposit(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
-                           const flux::map &m, const flux::field &f, const double *packed, const double *fpol,
-                           const double *edges, const size_t ns, const double sscale, const bool is_private,
-                           const unsigned int block, const size_t max_workgroups, const size_t lds_bytes,
-                           void *state, unsigned long long *counters, hipStream_t stream) {
+                           const cell_tables &t, const double *edges, const size_t ns, const double sscale,
+                           const launch_shape &shape, const cell_target &to) {
     if (count == 0) return;
-    if (is_f32) {
-        deposit_as<float> (columns, first, count, m, f, packed, fpol, edges, ns, sscale, is_private, block, max_workgroups,
-                           lds_bytes, state, counters, stream);
-    } else {
-        deposit_as<double> (columns, first, count, m, f, packed, fpol, edges, ns, sscale, is_private, block, max_workgroups,
-                            lds_bytes, state, counters, stream);
-    }
+    with_particle_type(is_f32, [&](auto type) {
+        using T = decltype(type);
+        launch_on_route(moment_deposit_kernel<true, T>, moment_deposit_kernel<false, T>, shape,
+                        grid_of(count, shape.block, shape.max_workgroups), to.stream,
+                        columns_from<T> (columns, first, columns[7] != nullptr), static_cast<unsigned long long> (count), t.map,
+                        t.field, t.packed, t.fpol, edges, static_cast<int> (ns), sscale,
+                        static_cast<unsigned long long *> (to.state), to.counters);
+    });
 }
 
 void launch_moment_deposit_particles(const void *const *columns, const bool is_f32, const size_t first, const size_t count,
-                                     const unsigned long long first_particle, const size_t batch_count, const flux::map &m,
-                                     const flux::field &f, const double *packed, const double *fpol, const double *edges,
-                                     const size_t ns, const double sscale, const bool is_private, const unsigned int block,
-                                     const size_t max_workgroups, const size_t lds_bytes, void *state,
-                                     unsigned long long *counters, hipStream_t stream) {
+                                     const unsigned long long first_particle, const size_t batch_count, const cell_tables &t,
+                                     const double *edges, const size_t ns, const double sscale, const launch_shape &shape,
+                                     const cell_target &to) {
     if (count == 0) return;
-    if (is_f32) {
-        deposit_particles_as<float> (columns, first, count, first_particle, batch_count, m, f, packed, fpol, edges, ns, sscale,
-                                     is_private, block, max_workgroups, lds_bytes, state, counters, stream);
-    } else {
-        deposit_particles_as<double> (columns, first, count, first_particle, batch_count, m, f, packed, fpol, edges, ns, sscale,
-                                      is_private, block, max_workgroups, lds_bytes, state, counters, stream);
-    }
+    with_particle_type(is_f32, [&](auto type) {
+        using T = decltype(type);
+        launch_on_route(moment_deposit_particles_kernel<true, T>, moment_deposit_particles_kernel<false, T>, shape,
+                        batched_grid_of(count, shape.block, shape.max_workgroups, batch_count), to.stream,
+                        columns_from<T> (columns, first, columns[7] != nullptr), static_cast<unsigned long long> (count),
+                        first_particle, static_cast<unsigned int> (batch_count), t.map, t.field, t.packed, t.fpol, edges,
+                        static_cast<int> (ns), sscale, static_cast<unsigned long long *> (to.state), to.counters);
+    });
 }
 
-void launch_moment_values(const void *const *columns, const bool is_f32, const size_t count, const flux::map &m,
-                          const flux::field &f, const double *packed, const double *fpol, double *label, double *values,
-                          hipStream_t stream) {
+void launch_moment_values(const void *const *columns, const bool is_f32, const size_t count, const cell_tables &t,
+                          double *label, double *values, hipStream_t stream) {
     if (count == 0) return;
-    const dim3 grid(static_cast<unsigned int> ((count + 255)/256));
-    if (is_f32) {
-        hipLaunchKernelGGL(moment_values_kernel<float>, grid, dim3(256), 0, stream, columns_from<float> (columns, 0, false),
-                           static_cast<unsigned long long> (count), m, f, packed, fpol, label, values);
-    } else {
-        hipLaunchKernelGGL(moment_values_kernel<double>, grid, dim3(256), 0, stream, columns_from<double> (columns, 0, false),
-                           static_cast<unsigned long long> (count), m, f, packed, fpol, label, values);
-    }
+    with_particle_type(is_f32, [&](auto type) {
+        using T = decltype(type);
+        hipLaunchKernelGGL(moment_values_kernel<T>, dim3(static_cast<unsigned int> ((count + 255)/256)), dim3(256), 0, stream,
+                           columns_from<T> (columns, 0, false), static_cast<unsigned long long> (count), t.map, t.field, t.packed,
+                           t.fpol, label, values);
+    });
 }
 
 }  // namespace gfhip

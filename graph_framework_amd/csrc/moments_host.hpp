@@ -18,6 +18,7 @@
 #include <limits>
 
 #include "flux_label.hpp"
+#include "point_host.hpp"
 #include "ray_batches.hpp"
 #include "superacc.hpp"
 
@@ -26,12 +27,8 @@ namespace moments {
 
 constexpr size_t count = 4;                            // density, current, energy, radiation
 
-//  The caller's tables: coefficients [16][table], fpol [4][intervals].
-struct host_tables {
-    const double *coefficients;
-    size_t table;
-    const double *fpol[4];
-};
+//  The caller's tables: coefficients [16][table], fpol [4][intervals] (point_host.hpp).
+using host_tables = flux::host_tables;
 
 //  The surface of `label` among the ns + 1 increasing edges, edge[i] <= label < edge[i+1], or -1: outside or NaN.
 inline long long host_cell(const double *edges, const size_t ns, const double label) {
@@ -42,18 +39,13 @@ inline long long host_cell(const double *edges, const size_t ns, const double la
 //  The label and the four moments of one particle, all the quiet NaN off the map.
 inline double host_point(const flux::map &m, const flux::field &f, const host_tables &t, const double x, const double y,
                          const double z, const double ux, const double uy, const double uz, const double gamma, double *values) {
-    double tr, tz, tp, gr, gz, c[16], cubic[4];
-    const long long at = flux::locate(m, x, y, z, tr, tz);
-    if (at < 0) {
+    flux::host_point_values p;
+    if (!flux::host_point(m, f, t, x, y, z, p)) {
         for (size_t k = 0; k < count; k++) values[k] = std::numeric_limits<double>::quiet_NaN();
         return std::numeric_limits<double>::quiet_NaN();
     }
-    for (size_t k = 0; k < 16; k++) c[k] = t.coefficients[k*t.table + static_cast<size_t> (at)];
-    const double psi = flux::psi_gradient(m, c, tr, tz, gr, gz);
-    const int q = flux::fpol_interval(f, psi, tp);
-    for (size_t k = 0; k < 4; k++) cubic[k] = t.fpol[k][q];
-    flux::moments_of(x, y, flux::radius_of(x, y), ux, uy, uz, gamma, gr, gz, flux::fpol_of(cubic, tp), values);
-    return flux::canonical(flux::label_of(m, psi));
+    flux::moments_of(x, y, flux::radius_of(x, y), ux, uy, uz, gamma, p.gr, p.gz, p.fpol, values);
+    return p.label;
 }
 
 //  label[s] and values[s*4 + k] of `particles` particles.  columns: x, y, z, ux, uy, uz, gamma, all of T.

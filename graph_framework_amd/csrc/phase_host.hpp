@@ -26,18 +26,13 @@ namespace phase {
 //  The label and the pitch cosine of one particle, both the quiet NaN off the map.
 inline void host_point(const flux::map &m, const flux::field &f, const moments::host_tables &t, const double x, const double y,
                        const double z, const double ux, const double uy, const double uz, double &label, double &pitch) {
-    double tr, tz, tp, gr, gz, c[16], cubic[4];
-    const long long at = flux::locate(m, x, y, z, tr, tz);
-    if (at < 0) {
+    flux::host_point_values p;
+    if (!flux::host_point(m, f, t, x, y, z, p)) {
         label = pitch = std::numeric_limits<double>::quiet_NaN();
         return;
     }
-    for (size_t k = 0; k < 16; k++) c[k] = t.coefficients[k*t.table + static_cast<size_t> (at)];
-    const double psi = flux::psi_gradient(m, c, tr, tz, gr, gz);
-    label = flux::canonical(flux::label_of(m, psi));
-    const int q = flux::fpol_interval(f, psi, tp);
-    for (size_t k = 0; k < 4; k++) cubic[k] = t.fpol[k][q];
-    pitch = flux::pitch_of(x, y, flux::radius_of(x, y), ux, uy, uz, gr, gz, flux::fpol_of(cubic, tp));
+    label = p.label;
+    pitch = flux::pitch_of(x, y, flux::radius_of(x, y), ux, uy, uz, p.gr, p.gz, p.fpol);
 }
 
 //  The deposit of `particles` particles, particle s of the columns being particle first_particle + s of the ensemble.

@@ -2,8 +2,9 @@
 //  host code under the address and undefined-behaviour sanitizers; no device is touched.  From graph_framework_amd/csrc:
 //
 //      hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -I../../include \
-//          -o /tmp/spectrum_host_check ../../profiles/diag/spectrum_host_check.cpp gf_hip.cpp reduce.hip deposition.hip \
-//          flux_profile.hip flux_spectrum.hip hand_over.hip cli_distribution.cpp -lhiprtc && /tmp/spectrum_host_check
+//          -o /tmp/spectrum_host_check ../../profiles/diag/spectrum_host_check.cpp gf_hip.cpp cells_rays.cpp cells_particles.cpp \
+//          reduce.hip deposition.hip flux_profile.hip flux_spectrum.hip phase_bins.hip moment_bins.hip confinement.hip \
+//          particle_source.hip hand_over.hip cli_distribution.cpp -lhiprtc && /tmp/spectrum_host_check
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
